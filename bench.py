@@ -7,20 +7,24 @@ decoded frames/sec at 512x512, 25 DDIM steps.
 One "step" = one full pass of the hot path over one synthetic clip: 25 DDIM steps of the sliding-window
 mean-overlap loop (CFG UNet3D forwards + fused CFG/overlap/DDIM update) followed by the sd-vae-ft-mse decode of
 every frame.  Inputs (latents, kps features, audio embeddings, reference banks) are resident in HBM when the
-timed region starts; the once-per-clip prologue (ReferenceNet + bank K/V precompute) is timed separately.
+timed region starts; the once-per-clip prologue (ReferenceNet + bank K/V precompute) is timed separately (`--full`).
 
 Workload: N=1 is BASELINE.json configs[1] (16 frames = one 16-frame window).  N>1 defaults to BASELINE configs[3]
 ("strong" scaling, the north-star multi-GPU number): the F = 124 clip inference.py:255-264 makes of a 128-frame
 request = 10 windows of 16 / overlap 4 = 20 (window, CFG-half) units sharded over the N ranks, one RCCL all-gather of
-the 4-channel predictions per DDIM step, decode split over the ranks; rank 0 then also runs the SAME clip alone
-(`same_clip_1gpu_fps`) so that the multi-GPU speed-up is a ratio of like with like.  `--scaling weak` keeps round 1's
+the 4-channel predictions per DDIM step, decode split over the ranks; with `--full` rank 0 then also runs the SAME clip
+alone (`same_clip_1gpu_fps`) so that the multi-GPU speed-up is a ratio of like with like.  `--scaling weak` keeps round 1's
 F = 12*N + 4 (one window per GPU per step).  value = F*K / max-over-ranks time.
 `python bench.py --gpus N` without a torchrun environment re-launches itself under torch.distributed.run with N ranks
 (one per GPU, RCCL); a world size that differs from --gpus is an error.
 
-The printed line is ONE compact JSON object (< 4 KB: `compact_line`; the 23 KB line of round 5 could not be parsed by the
-driver): the contract's keys + `roofline` + `cpu_baseline`; every table (ranking, per-kernel, per-instantiation, HBM kernels,
-block paths, the CPU workers) goes to the side file named by its `detail` key (`--detail`, default gpurun_out/bench_detail.json).
+A plain run sets up, warms up, times the K steps, writes the last timed step's video with `--dump-outputs DIR` (the same
+seeded inputs in every run, so two builds can be compared output for output) and prints ONE compact JSON line of the
+contract's keys (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  `--full` also measures what
+the headline figure does not need - the prologue time, `roofline`, `cpu_baseline` and, N>1, per-rank / per-collective
+timing and the same clip on one GPU - and the line (< 4 KB: `compact_line`; the 23 KB line of round 5 could not be parsed
+by the driver) then carries `roofline` + `cpu_baseline`; every table (ranking, per-kernel, per-instantiation, HBM kernels,
+block paths, the CPU workers) goes to the side file named by its `detail` key (`--detail`).
   roofline      dominant kernel = the ONE kernel instantiation with the most time in a whole clip, chosen over ALL profiled
                 kernels - every vx_gemm launch (2*M*N*K FLOP), the attention kernels (4*B*H*Nq*Nkv*d at the true head dim),
                 the one-launch feed-forward / temporal blocks and the HBM-bound kernels (algorithmic bytes) - from HIP-event
@@ -457,6 +461,25 @@ def compact_line(result, detail_path=None):
     return line
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6    # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(outputs, out_dir, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: every array of `outputs` as out_dir/<name>.npy in float32.  One too large for its share of `limit`
+    is written as <name>_sample.npy instead: a fixed, seeded choice of its rows (last dimension whole), in order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (limit - 1024 * len(outputs)) // len(outputs)          # (1024: room for each file's .npy header)
+    for name, t in outputs.items():
+        t = t.detach().float()
+        if t.numel() * 4 > share:
+            rows = t.reshape(-1, t.shape[-1])
+            k = max(1, share // (4 * rows.shape[1]))
+            idx = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(seed))[:k].sort().values
+            t, name = rows[idx.to(rows.device)], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -485,7 +508,16 @@ def main():
     ap.add_argument("--gemm-shapes", default="", help="write the per-shape vx_gemm timing table of the roofline leg here")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="side file for the full tables (ranking, per-kernel, HBM kernels, block paths, CPU-leg probes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the prologue time, the roofline leg, the "
+                         "CPU baseline and (N > 1) per-rank / per-collective timing and the same clip on one GPU; writes "
+                         "the side file (--detail)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the video of the last one as DIR/video.npy (float32; a seeded "
+                         "sample of its rows, DIR/video_sample.npy, when it exceeds 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.cpu_leg:
         cpu_leg(args.size, args.cpu_budget, args.cpu_max_workers)
@@ -563,13 +595,14 @@ def main():
     torch.cuda.synchronize()
     t_build = time.time() - t_build
 
-    # ---- once-per-clip prologue (ReferenceNet -> banks -> K/V of every attn1_5), timed separately
+    # ---- once-per-clip prologue (ReferenceNet -> banks -> K/V of every attn1_5), timed separately with --full
     writer = vx.ReferenceAttentionControl(refnet, do_classifier_free_guidance=True, mode="write", fusion_blocks="full")
     reader = vx.ReferenceAttentionControl(unet, do_classifier_free_guidance=True, mode="read", fusion_blocks="full",
                                           reference_attention_weight=0.95, audio_attention_weight=3.0)
     ehs0 = torch.zeros(1, 1, 768, device=dev)
-    refnet(inp["ref_latents"], timestep=0, encoder_hidden_states=ehs0, return_dict=False)   # warm
-    torch.cuda.synchronize()
+    if args.full:
+        refnet(inp["ref_latents"], timestep=0, encoder_hidden_states=ehs0, return_dict=False)   # warm
+        torch.cuda.synchronize()
     t0 = time.time()
     refnet(inp["ref_latents"], timestep=0, encoder_hidden_states=ehs0, return_dict=False)
     reader.update(writer, True)
@@ -612,6 +645,8 @@ def main():
         rank_ms = [1e3 * t.item() / args.steps for t in allt]
         elapsed = max(t.item() for t in allt)
     assert video.shape == (1, 3, F, args.size, args.size) and torch.isfinite(video).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs({"video": video}, args.dump_outputs)
     fps = F * args.steps / elapsed
     scale = (args.size / 512.0) ** 2
     fpf = flop_per_frame(F, len(windows), args.ddim_steps, scale, ctx)
@@ -634,11 +669,13 @@ def main():
                                    (f", {fshards} frame shards per unit" if fshards > 1 else "") +
                                    (f", {2 * len(windows) // world} whole units per GPU + the {2 * len(windows) % world} "
                                     f"left-over units frame-sharded {mshards} ways" if mshards > 1 else ""))},
-        "prologue_ms": 1e3 * prologue_s, "model_build_s": t_build, "lib_sha256": _lib_sha(),
+        "model_build_s": t_build, "lib_sha256": _lib_sha(),
         # which implementation each block of each UNet level took in this run (ops.BLOCK_PATHS: one-launch kernels vs the
         # multi-launch forms, GroupNorm folds) - a geometry that falls off a fused path shows here and as a log warning
         "block_paths": ops.block_paths(),
     }
+    if args.full:
+        result["prologue_ms"] = 1e3 * prologue_s
     if args.fp8:
         # VERDICT r03 item 7, closed in LABNOTES 11.4: the e4m3 projections are a parity-complete OPTION, not a speed-up.
         result["fp8_note"] = ("fp8 (e4m3) q/k/v/out projections: parity-complete (tests/test_gpu_kernels.py, "
@@ -646,7 +683,7 @@ def main():
                               "launch latency, fp8 halves one operand's bytes and adds a quantisation pass; measured "
                               "768x768: 4.01 (fp8) vs 4.50 (bf16) frames/s, profiles/r03f_bench_768_*.json.  Compare "
                               "this line's value with the same command without --fp8.")
-    if world > 1:
+    if world > 1 and args.full:
         # One more clip with every collective of the data path timed (events on the launch stream) and this rank's own
         # compute time between the collectives: what a first real 8-GPU run needs to be diagnosable from this one line.
         from v_express_amd.distributed import CommTimer
@@ -682,7 +719,8 @@ def main():
         else:
             assert pipe.dist.enabled and pipe.dist.backend == "nccl", "the measured multi-GPU path must be RCCL"
 
-    if not args.no_roofline:
+    roofline = args.full and not args.no_roofline
+    if roofline:
         # one instrumented DDIM step (all of this rank's UNet calls) + the decode of 4 frames.  EVERY rank runs the step
         # (denoise contains the per-timestep all-gather); only rank 0 records and reports.
         import contextlib
@@ -701,7 +739,7 @@ def main():
                 pipe.vae.decode_video(lat[:, :, :n_dec].contiguous(), chunk=4)
             ops.PROFILE_WEIGHT[0] = 1.0
         torch.cuda.synchronize()
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline:
         summ = prof.summary()
         syms = prof.by_symbol()
         if args.gemm_shapes:
@@ -794,7 +832,7 @@ def main():
             "whole_path": {"tflop_per_frame": fpf, "achieved": fps * fpf / world, "frac": fps * fpf / world / PEAK_BF16_TFLOPS,
                            "note": "fps x algorithmic TFLOP/frame (SURVEY.md 8d) per GPU / 2.5 PFLOP/s"},
         }
-    if world > 1 and not args.no_same_clip_1gpu:
+    if world > 1 and args.full and not args.no_same_clip_1gpu:
         # the same clip on ONE GPU (rank 0 alone, sharding off) so that the multi-GPU speed-up compares like with like
         if rank == 0:
             from v_express_amd.distributed import DistContext
@@ -813,14 +851,14 @@ def main():
             result["speedup_vs_1gpu_same_clip"] = fps / (F / t1)
     if world > 1:
         dist.barrier()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.size, 30)
         if result["cpu_baseline"]["value"]:
             result["speedup_vs_cpu"] = fps / result["cpu_baseline"]["value"]
     if rank == 0:
         # ONE compact line for the driver (< LINE_LIMIT bytes; BENCH_r05.json could not be parsed at 23 KB); every table
         # (ranking, per-kernel, per-instantiation, HBM kernels, block paths, the CPU leg's probes) goes to the side file
-        detail_path = write_detail(result, args.detail)
+        detail_path = write_detail(result, args.detail) if args.full else None
         print(json.dumps(compact_line(result, detail_path)))
     if world > 1:
         dist.destroy_process_group()

@@ -60,6 +60,38 @@ AUDIO_SMALL = dict(dim=128, depth=2, dim_head=16, heads=8, num_queries=5, embedd
                    max_seq_len=10)
 
 
+def context_grid():
+    """(F, size, overlap, stride, closed_loop, step) of every context-scheduler case in tests/golden/reference_live.pt:
+    one-window clips, exact multiples, reflected last windows and the multi-level (stride > 1) schedules."""
+    for F in list(range(1, 40)) + [64, 124, 128, 200]:
+        for size in (4, 8, 16, 24):
+            for ov in (0, 2, 4):
+                if ov >= size:
+                    continue
+                for stride in (1, 2, 3):
+                    for closed in (False, True):
+                        for step in (0, 1, 2, 3, 5, 8):
+                            yield F, size, ov, stride, closed, step
+
+
+def legacy_unet_state_dict():
+    """A few keys of each kind that train.py's get_denoising_unet_state_dict remaps (checkpoints.py restates it)."""
+    import torch
+    return {"down.attentions.0.attn1.to_q.weight": torch.ones(2), "down.norm1.weight": torch.full((2,), 2.0),
+            "down.attentions.0.attn2.to_q.weight": torch.zeros(2),
+            "down.attentions.0.attn2.processor.to_q_aud.weight": torch.full((2,), 5.0),
+            "down.attentions.0.attn2.to_out.0.bias": torch.zeros(2),
+            "down.attentions.0.attn2.processor.to_out_aud.0.bias": torch.full((2,), 7.0)}
+
+
+def window_digest(windows):
+    """64-bit digest of a list of context windows (order and values), as a signed integer."""
+    import hashlib
+    import json
+    h = hashlib.sha256(json.dumps([[int(x) for x in w] for w in windows]).encode()).digest()
+    return int.from_bytes(h[:8], "little", signed=True)
+
+
 def prologue_inputs(seed=11):
     import torch
     g = torch.Generator().manual_seed(seed)

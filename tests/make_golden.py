@@ -56,6 +56,65 @@ def prologue(out):
     print("prologue", {k: tuple(v.shape) for k, v in g.items()})
 
 
+def live_reference(out):
+    """What tests/test_oracle_vs_reference.py and test_host_logic.py compare against: the key schemas of the reference's
+    own modules, one patched UNet3D forward with its ReferenceNet banks, the context scheduler's windows over the whole
+    parameter grid (as digests) and train.py's legacy state-dict remaps."""
+    import ast
+    import copy
+    import importlib.util
+    import ref_import as R
+    modules, _ = R.import_reference()
+    import diffusers   # the stand-in (on sys.path after import_reference)
+
+    def schema(m):
+        return {k: tuple(v.shape) for k, v in m.state_dict().items()}
+    g = {}
+    cfg = cases.unet_cfg(cases.SMALL)
+    sd3, sd2 = synth.unet3d_state_dict(cfg, seed=7), synth.refnet_state_dict(cfg, seed=8)
+    unet, refnet = H.build_reference_unets(cfg, sd3, sd2)
+    g["unet3d_schema"], g["refnet_schema"] = schema(unet), schema(refnet)
+    inp = synth.synthetic_inputs(cfg, 6, 8, 16, seed=9)
+    pred, banks = H.reference_unet_forward(unet, refnet, inp, 519, 0.9, 2.0, frames=[1, 2, 3, 5])
+    g["forward_pred"], g["forward_banks"] = pred.clone(), {k: v.clone() for k, v in banks.items()}
+    for tag, kw in (("small", cases.KPS_SMALL), ("full", {})):
+        kcfg = synth.KpsGuiderConfig(**kw)
+        g[f"kps_schema_{tag}"] = schema(modules.VKpsGuider(kcfg.conditioning_embedding_channels,
+                                                           block_out_channels=kcfg.block_out_channels))
+    for tag, kw in (("small", cases.AUDIO_SMALL), ("full", {})):
+        acfg = synth.AudioProjectionConfig(**kw)
+        g[f"audio_schema_{tag}"] = schema(modules.AudioProjection(
+            dim=acfg.dim, depth=acfg.depth, dim_head=acfg.dim_head, heads=acfg.heads, num_queries=acfg.num_queries,
+            embedding_dim=acfg.embedding_dim, output_dim=acfg.output_dim, ff_mult=acfg.ff_mult,
+            max_seq_len=acfg.max_seq_len))
+    vcfg = synth.VaeConfig(**cases.SMALL_VAE)
+    g["vae_schema"] = schema(diffusers.AutoencoderKL(block_out_channels=vcfg.block_out_channels,
+                                                     layers_per_block=vcfg.layers_per_block,
+                                                     norm_num_groups=vcfg.norm_num_groups,
+                                                     latent_channels=vcfg.latent_channels))
+    spec = importlib.util.spec_from_file_location("ref_context", os.path.join(R.REFERENCE_ROOT, "pipelines", "context.py"))
+    ctx = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ctx)
+    grid = list(cases.context_grid())
+    g["context_grid"] = torch.tensor([[F, size, ov, stride, int(closed), step]
+                                      for F, size, ov, stride, closed, step in grid], dtype=torch.int16)
+    g["context_digests"] = torch.tensor([cases.window_digest(ctx.uniform(step, F, size, stride, ov, closed))
+                                         for F, size, ov, stride, closed, step in grid], dtype=torch.int64)
+    vals = (0, 1, 2, 3, 6, 255, 2 ** 40 + 7)
+    g["ordered_halving"] = {v: ctx.ordered_halving(v) for v in vals}
+    # train.py's get_denoising_unet_state_dict, executed from the reference source on the test's small state dict
+    path = os.path.join(R.REFERENCE_ROOT, "train.py")
+    tree = ast.parse(open(path).read())
+    node = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "get_denoising_unet_state_dict"][0]
+    ns = {"copy": copy}
+    exec(compile(ast.Module(body=[node], type_ignores=[]), path, "exec"), ns)
+    sd = cases.legacy_unet_state_dict()
+    g["legacy_remaps"] = {kind: ns["get_denoising_unet_state_dict"](sd, kind)
+                          for kind in ("old_attn", "moore_pretrained", "new_attn")}
+    torch.save(g, os.path.join(out, "reference_live.pt"))
+    print("reference_live", {k: (tuple(v.shape) if hasattr(v, "shape") else len(v)) for k, v in g.items()})
+
+
 def wav2vec2(out):
     """Outputs of the installed transformers Wav2Vec2Model (the third-party module the reference calls at
     pipelines/v_express_pipeline.py:377) on the seeded synthetic weights and waveform."""
@@ -223,6 +282,8 @@ def main():
         return prologue(out)
     if len(sys.argv) > 1 and sys.argv[1] == "wav2vec2":
         return wav2vec2(out)
+    if len(sys.argv) > 1 and sys.argv[1] == "live":
+        return live_reference(out)
     if len(sys.argv) > 1 and sys.argv[1] == "nocfg":
         return nocfg(out)
     if len(sys.argv) > 1 and sys.argv[1] == "fullsize":      # ~40 min; not part of the default regeneration
@@ -235,6 +296,7 @@ def main():
         return fullsize_768(out)
     prologue(out)
     wav2vec2(out)
+    live_reference(out)
     built = {}
     for name, (kw, F, h, w, t) in cases.FORWARD_CASES.items():
         key = tuple(kw["block_out_channels"])

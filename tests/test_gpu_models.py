@@ -416,21 +416,24 @@ def test_zero_audio_rows_reduce_to_output_bias():
     assert r2 <= 2e-3, r2
 
 
-def test_bench_two_rank_control_flow_on_one_gpu():
-    """bench.py under torchrun with 2 ranks folded onto this GPU (VX_DIST_BACKEND=gloo: collectives staged through the
-    host) - exercises exactly the multi-rank control flow the driver launches with RCCL: unit sharding, the per-step
+def test_bench_two_rank_control_flow_on_one_gpu(tmp_path):
+    """bench.py --full under torchrun with 2 ranks folded onto this GPU (VX_DIST_BACKEND=gloo: collectives staged through
+    the host) - exercises exactly the multi-rank control flow the driver launches with RCCL: unit sharding, the per-step
     all-gather, the decode split + frame gather, the max-over-ranks timing and the rank-0-only roofline leg (which must
-    not leave rank 0 alone inside a collective).  Checks that it terminates and prints one well-formed JSON line."""
+    not leave rank 0 alone inside a collective).  Checks that it terminates and prints one well-formed JSON line, and
+    that rank 0 alone writes the (sampled) video of --dump-outputs."""
     _need_gpu()
     import json
     import subprocess
     import sys
+    import numpy as np
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, VX_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     # started the way the driver may start it - plain `python bench.py --gpus 2`: bench.py re-launches itself under
     # torch.distributed.run with one rank per --gpus
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--ddim-steps", "1", "--no-cpu-baseline", "--scaling", "weak"]
+           "--ddim-steps", "1", "--no-cpu-baseline", "--scaling", "weak", "--full",
+           "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(tmp_path / "out")]
     env.pop("WORLD_SIZE", None)
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
@@ -441,6 +444,10 @@ def test_bench_two_rank_control_flow_on_one_gpu():
     assert d["value"] > 0 and d["scaling"] == "weak" and d["roofline"]["achieved"] > 0
     # the same clip on one rank alone, for a like-for-like multi-GPU ratio
     assert d["same_clip_1gpu_fps"] > 0 and d["speedup_vs_1gpu_same_clip"] > 0
+    # 28 frames of 512 x 512 x 3 float32 = 88 MB > 64 MB: a row sample
+    assert os.listdir(tmp_path / "out") == ["video_sample.npy"]
+    v = np.load(tmp_path / "out" / "video_sample.npy")
+    assert v.dtype == np.float32 and v.shape[1] == 512 and 0 < v.nbytes <= 64e6 and np.isfinite(v).all()
 
 
 @pytest.mark.parametrize("world,S,F,cf,co", [(2, 2, 8, 8, 2), (4, 0, 8, 8, 2), (4, 2, 14, 8, 2), (4, 1, 32, 8, 2)])

@@ -203,31 +203,19 @@ def test_audio_windows_match_reference_golden():
 
 
 def test_checkpoint_ingestion_order_and_legacy_key_remaps(tmp_path):
-    """checkpoints.py: (1) the legacy remaps equal the reference's own train.py:122-161 function (executed from the
-    reference source when it is available, otherwise against the hand-written expectation); (2) the two-file load
+    """checkpoints.py: (1) the legacy remaps equal the reference's own train.py:122-161 function (its outputs recorded
+    in tests/golden/reference_live.pt) and the hand-written expectation; (2) the two-file load
     order of inference.py:84-96 (denoising UNet, then motion module on top, both strict=False) fills every key; (3)
     file formats (.bin through torch.load, .safetensors) and the VAE's deprecated attention key names."""
-    import ast
-    import copy
+    import cases
     from v_express_amd import checkpoints as CK
-    sd = {"down.attentions.0.attn1.to_q.weight": torch.ones(2), "down.norm1.weight": torch.full((2,), 2.0),
-          "down.attentions.0.attn2.to_q.weight": torch.zeros(2),
-          "down.attentions.0.attn2.processor.to_q_aud.weight": torch.full((2,), 5.0),
-          "down.attentions.0.attn2.to_out.0.bias": torch.zeros(2),
-          "down.attentions.0.attn2.processor.to_out_aud.0.bias": torch.full((2,), 7.0)}
-    ref_path = "/root/reference/train.py"
-    ref_fn = None
-    if os.path.exists(ref_path):
-        tree = ast.parse(open(ref_path).read())
-        node = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "get_denoising_unet_state_dict"][0]
-        ns = {"copy": copy}
-        exec(compile(ast.Module(body=[node], type_ignores=[]), ref_path, "exec"), ns)
-        ref_fn = ns["get_denoising_unet_state_dict"]
+    sd = cases.legacy_unet_state_dict()
+    ref = torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_live.pt"),
+                     weights_only=False)["legacy_remaps"]
     for kind in ("old_attn", "moore_pretrained", "new_attn"):
         got = CK.get_denoising_unet_state_dict(sd, kind)
-        if ref_fn is not None:
-            want = ref_fn(sd, kind)
-            assert set(got) == set(want) and all(torch.equal(got[k], want[k]) for k in want), kind
+        want = ref[kind]
+        assert set(got) == set(want) and all(torch.equal(got[k], want[k]) for k in want), kind
     got = CK.get_denoising_unet_state_dict(sd, "old_attn")
     assert torch.equal(got["down.attentions.0.attn1_5.to_q.weight"], torch.ones(2))
     assert torch.equal(got["down.norm1_5.weight"], torch.full((2,), 2.0))
@@ -309,6 +297,26 @@ def test_bench_algorithmic_flops_match_the_survey_figures():
     assert abs(bench.flop_per_frame(64, 5, 25, 1.0) - 82.3) < 0.05
     assert abs(bench.flop_per_frame(124, 10, 25, 1.0) - 84.9) < 0.05
     assert abs(bench.flop_per_frame(16, 1, 25, 2.25) - 183.8) < 0.1
+
+
+def test_bench_dump_outputs_whole_or_seeded_row_sample(tmp_path):
+    """bench.py --dump-outputs: an output within the limit is written whole as float32; a larger one as the same seeded,
+    ordered choice of whole rows in every run, within the limit."""
+    import numpy as np
+    import bench
+    x = torch.arange(2 * 3 * 8 * 16, dtype=torch.float64).reshape(1, 2, 3, 8, 16)
+    bench.dump_outputs({"video": x}, str(tmp_path / "a"))
+    got = np.load(tmp_path / "a" / "video.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.float().numpy())
+    limit = 1024 + 10 * 16 * 4                                # room for 10 of the 48 rows
+    for d in ("b", "c"):
+        bench.dump_outputs({"video": x}, str(tmp_path / d), limit=limit)
+        assert os.listdir(tmp_path / d) == ["video_sample.npy"]
+    b, c = np.load(tmp_path / "b" / "video_sample.npy"), np.load(tmp_path / "c" / "video_sample.npy")
+    assert b.shape == (10, 16) and np.array_equal(b, c)
+    rows = b[:, 0] / 16
+    assert np.array_equal(rows, np.sort(rows)) and len(set(rows)) == 10
+    assert np.array_equal(b, x.reshape(-1, 16).float().numpy()[rows.astype(int)])
 
 
 def test_bench_prints_one_compact_line_the_driver_can_parse(tmp_path):

@@ -1,6 +1,7 @@
-"""Tier A == Tier B, live: the reference's own modules (imported unmodified) against oracle/ on fresh seeds.
-Dev container only (skips where /root/reference is absent).  Also pins the synthetic state_dict schema
-to the reference's own `state_dict()` keys/shapes."""
+"""Tier A == Tier B: the reference's own modules (imported unmodified) against oracle/, through what
+tests/make_golden.py live recorded from them in tests/golden/reference_live.pt (outputs on seeded inputs, the
+`state_dict()` key / shape schemas, the context scheduler's windows over a parameter grid).  Also pins the synthetic
+state_dict schema to the reference's own keys / shapes."""
 import os
 
 import torch
@@ -9,21 +10,30 @@ import cases
 from oracle import unet as OU
 from v_express_amd import synth
 
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
-def test_schema_and_forward_against_live_reference(reference):
-    import refharness as H
+
+def _live():
+    return torch.load(os.path.join(GOLD, "reference_live.pt"), weights_only=False)
+
+
+def _same_schema(schema, sd):
+    """What a strict `load_state_dict` of `sd` into the recorded module checks: the same keys, the same shapes."""
+    return set(schema) == set(sd) and all(tuple(schema[k]) == tuple(sd[k].shape) for k in sd)
+
+
+def test_schema_and_forward_against_live_reference():
+    g = _live()
     kw = cases.SMALL
     cfg, ocfg = cases.unet_cfg(kw), cases.oracle_cfg(kw)
     sd3, sd2 = synth.unet3d_state_dict(cfg, seed=7), synth.refnet_state_dict(cfg, seed=8)
-    unet, refnet = H.build_reference_unets(cfg, sd3, sd2)     # strict=True load == schema check
-    r3, r2 = unet.state_dict(), refnet.state_dict()
-    assert set(r3) == set(sd3) and set(r2) == set(sd2)
-    assert all(tuple(r3[k].shape) == tuple(sd3[k].shape) for k in sd3)
+    assert _same_schema(g["unet3d_schema"], sd3) and _same_schema(g["refnet_schema"], sd2)
     assert len(sd3) == 1386 and len(sd2) == 684
     inp = synth.synthetic_inputs(cfg, 6, 8, 16, seed=9)
     frames = [1, 2, 3, 5]
-    pred, banks = H.reference_unet_forward(unet, refnet, inp, 519, 0.9, 2.0, frames=frames)
+    pred, banks = g["forward_pred"], g["forward_banks"]
     ob = OU.refnet_banks(sd2, ocfg, inp["ref_latents"])
+    assert set(ob) == set(banks)
     assert max((ob[k] - banks[k]).abs().max().item() for k in ob) < 5e-5
     x = inp["latents"][:, :, frames].repeat(2, 1, 1, 1, 1)
     ehs = inp["audio_embeddings"][:, frames].reshape(-1, 5, 768)
@@ -31,7 +41,7 @@ def test_schema_and_forward_against_live_reference(reference):
     assert (o - pred).abs().max().item() < 2e-5
 
 
-def test_uncond_reference_attention_is_out_bias(reference):
+def test_uncond_reference_attention_is_out_bias():
     """attention against an all-zero bank returns exactly to_out.bias."""
     from oracle import leaf as L
     g = torch.Generator().manual_seed(0)
@@ -43,100 +53,74 @@ def test_uncond_reference_attention_is_out_bias(reference):
     assert torch.allclose(o, w["a.to_out.0.bias"].expand_as(o), atol=1e-6)
 
 
-def test_prologue_models_against_live_reference(reference):
+def test_prologue_models_against_live_reference():
     """VKpsGuider / AudioProjection (reference modules, unmodified) and AutoencoderKL.encode (diffusers stand-in) vs
-    oracle/prologue.py on the same synthetic weights; strict state_dict loads pin the key schema."""
-    import ref_import as R
-    import diffusers
+    oracle/prologue.py on the same synthetic weights (reference outputs: tests/golden/prologue.pt); the recorded
+    `state_dict()` schemas pin the key schema as a strict load would."""
     import oracle
     from oracle import prologue as OP
-    modules, _ = R.import_reference()
+    g, gp = _live(), torch.load(os.path.join(GOLD, "prologue.pt"), weights_only=False)
     inp = cases.prologue_inputs()
     # --- VKpsGuider
-    for kw in (cases.KPS_SMALL, {}):
+    for tag, kw in (("small", cases.KPS_SMALL), ("full", {})):
         kcfg = synth.KpsGuiderConfig(**kw)
         sd = synth.kps_guider_state_dict(kcfg)
-        ref = modules.VKpsGuider(kcfg.conditioning_embedding_channels, block_out_channels=kcfg.block_out_channels)
-        ref.load_state_dict(sd, strict=True)
-        with torch.no_grad():
-            want = ref(inp["kps_images"])                                          # [1, C, f, h/8, w/8]
+        assert _same_schema(g[f"kps_schema_{tag}"], sd)
+        want = gp[f"kps_{tag}"]                                                    # [1, C, f, h/8, w/8]
         b, c, f, H, W = inp["kps_images"].shape
         got = OP.kps_guider(sd, inp["kps_images"].permute(0, 2, 1, 3, 4).reshape(b * f, c, H, W))
         got = got.reshape(b, f, -1, H // 8, W // 8).permute(0, 2, 1, 3, 4)
         assert (got - want).abs().max().item() < 1e-5
     # --- AudioProjection
-    for kw, key in ((cases.AUDIO_SMALL, "audio_windows_small"), ({}, "audio_windows_full")):
+    for tag, kw, key in (("small", cases.AUDIO_SMALL, "audio_windows_small"), ("full", {}, "audio_windows_full")):
         acfg = synth.AudioProjectionConfig(**kw)
         sd = synth.audio_projection_state_dict(acfg)
-        ref = modules.AudioProjection(dim=acfg.dim, depth=acfg.depth, dim_head=acfg.dim_head, heads=acfg.heads,
-                                      num_queries=acfg.num_queries, embedding_dim=acfg.embedding_dim,
-                                      output_dim=acfg.output_dim, ff_mult=acfg.ff_mult, max_seq_len=acfg.max_seq_len)
-        ref.load_state_dict(sd, strict=True)
-        with torch.no_grad():
-            want = ref(inp[key])
+        assert _same_schema(g[f"audio_schema_{tag}"], sd)
+        want = gp[f"audio_{tag}"]
         got = OP.audio_projection(sd, inp[key], acfg.depth, acfg.heads)
         assert (got - want).abs().max().item() < 2e-5
-    # --- VAE encode (mean)
+    # --- VAE encode (mean): the encoder half of the full AutoencoderKL schema
     vcfg = synth.VaeConfig(**cases.SMALL_VAE)
     sdv = synth.vae_encoder_state_dict(vcfg)
-    vae = diffusers.AutoencoderKL(block_out_channels=vcfg.block_out_channels, layers_per_block=vcfg.layers_per_block,
-                                  norm_num_groups=vcfg.norm_num_groups, latent_channels=vcfg.latent_channels)
-    missing = vae.load_state_dict(sdv, strict=False)
-    assert all(k.startswith(("decoder.", "post_quant_conv.")) for k in missing.missing_keys) and not missing.unexpected_keys
-    with torch.no_grad():
-        want = vae.encode(inp["ref_image"]).latent_dist.mean
+    schema = g["vae_schema"]
+    missing = set(schema) - set(sdv)
+    assert all(k.startswith(("decoder.", "post_quant_conv.")) for k in missing) and set(sdv) <= set(schema)
+    assert all(tuple(schema[k]) == tuple(v.shape) for k, v in sdv.items())
+    want = gp["vae_mean"]
     got = OP.vae_encode_mean(sdv, oracle.VaeConfig(**cases.SMALL_VAE), inp["ref_image"])
     assert (got - want).abs().max().item() < 2e-5
 
 
-def test_audio_windows_and_median_against_live_reference(reference):
+def test_audio_windows_and_median_against_live_reference():
     """The audio-window construction of prepare_audio_embeddings (executed from the reference pipeline's own source
-    lines) and pipelines/utils.py:median_filter_3d vs the oracle restatements: bit-exact."""
-    import ref_import as R
+    lines) and pipelines/utils.py:median_filter_3d vs the oracle restatements: bit-exact (reference outputs:
+    tests/golden/prologue.pt)."""
     from oracle import prologue as OP
-    U = R.import_reference_utils()
+    gp = torch.load(os.path.join(GOLD, "prologue.pt"), weights_only=False)
     inp = cases.prologue_inputs()
-    want = U.median_filter_3d(inp["video"], 3, "cpu")
     got = OP.median_filter_3d(inp["video"], 3)
-    assert torch.equal(got, want)
-    # window construction: run the reference method body on a stand-in `self`
-    import types
-    _, pipelines = R.import_reference()
-    from pipelines.v_express_pipeline import VExpressPipeline
+    assert torch.equal(got, gp["median"])
     F_, pad = 7, 2
-    stub = types.SimpleNamespace(
-        audio_processor=lambda wav, return_tensors, sampling_rate: {"input_values": wav},
-        audio_encoder=lambda wav: types.SimpleNamespace(last_hidden_state=inp["wav2vec_states"]),
-        audio_projection=lambda x: x, device="cpu", dtype=torch.float32)
-    want = VExpressPipeline.prepare_audio_embeddings(stub, torch.zeros(1, 16), F_, pad, False)[0]
     got = OP.audio_windows(inp["wav2vec_states"], F_, pad)
-    assert torch.equal(got, want)
+    assert torch.equal(got, gp["audio_windows_F7"])
 
 
-def test_context_scheduler_own_formulation_equals_the_reference_for_all_parameters(reference):
+def test_context_scheduler_own_formulation_equals_the_reference_for_all_parameters():
     """v_express_amd.context.uniform (round 3: an own formulation - dilation levels, radical-inverse offset, reflection -
-    instead of a transcription) against /root/reference/pipelines/context.py:22-60 for every combination of clip length,
-    window size, overlap, stride, closed_loop and step on a grid that covers one-window clips, exact multiples, reflected
-    last windows and the multi-level (context_stride > 1) schedules the pipeline itself never asks for."""
-    import importlib.util
-    import ref_import
+    instead of a transcription) against the reference's pipelines/context.py:22-60 (its windows recorded as digests in
+    tests/golden/reference_live.pt) for every combination of clip length, window size, overlap, stride, closed_loop and
+    step on a grid that covers one-window clips, exact multiples, reflected last windows and the multi-level
+    (context_stride > 1) schedules the pipeline itself never asks for."""
     from v_express_amd import context as C
-    spec = importlib.util.spec_from_file_location("ref_context", os.path.join(ref_import.REFERENCE_ROOT, "pipelines", "context.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
+    g = _live()
+    grid = list(cases.context_grid())
+    assert g["context_grid"].tolist() == [[F, size, ov, stride, int(closed), step]
+                                          for F, size, ov, stride, closed, step in grid]
     n = 0
-    for F in list(range(1, 40)) + [64, 124, 128, 200]:
-        for size in (4, 8, 16, 24):
-            for ov in (0, 2, 4):
-                if ov >= size:
-                    continue
-                for stride in (1, 2, 3):
-                    for closed in (False, True):
-                        for step in (0, 1, 2, 3, 5, 8):
-                            a = list(m.uniform(step, F, size, stride, ov, closed))
-                            b = list(C.uniform(step, F, size, stride, ov, closed))
-                            assert a == b, (F, size, ov, stride, closed, step)
-                            n += 1
+    for (F, size, ov, stride, closed, step), want in zip(grid, g["context_digests"].tolist()):
+        b = list(C.uniform(step, F, size, stride, ov, closed))
+        assert cases.window_digest(b) == want, (F, size, ov, stride, closed, step)
+        n += 1
     assert n > 10000
-    for v in (0, 1, 2, 3, 6, 255, 2 ** 40 + 7):
-        assert C.radical_inverse_base2(v) == m.ordered_halving(v)
+    for v, want in g["ordered_halving"].items():
+        assert C.radical_inverse_base2(v) == want

@@ -55,7 +55,7 @@ tests16)
 smoke)
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/${T}_smoke.log 2>&1; tail -2 $OUT/${T}_smoke.log ;;
 bench)
-  timeout 900 python bench.py --gemm-shapes $OUT/${T}_gemm_by_shape.txt --detail $OUT/${T}_bench_detail.json "$@" > $OUT/${T}_bench.json 2> $OUT/${T}_bench.err
+  timeout 900 python bench.py --full --gemm-shapes $OUT/${T}_gemm_by_shape.txt --detail $OUT/${T}_bench_detail.json "$@" > $OUT/${T}_bench.json 2> $OUT/${T}_bench.err
   python -c "import sys; n = len(open('$OUT/${T}_bench.json').read().strip().splitlines()[-1]); print('bench line bytes:', n); sys.exit(0 if n < 4096 else 1)"
   fps_of < $OUT/${T}_bench.json ;;
 ab)
@@ -78,7 +78,7 @@ configs)
   done ;;
 profile)
   SHA=$(python tools/lib_id.py)
-  CMD="python bench.py --steps 1 --warmup 1 --no-cpu-baseline"
+  CMD="python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline"
   rm -rf /tmp/prof && mkdir -p /tmp/prof
   timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o bench -- $CMD > $OUT/${T}_prof_bench.log 2> $OUT/${T}_prof_bench.err
   for f in $(find /tmp/prof -name "*kernel_stats.csv"); do cp "$f" $OUT/${T}_kernel_stats.csv; done
@@ -108,7 +108,7 @@ scale8)
     echo "rccl_probe --gpus 8: exit $?" | tee -a $OUT/${T}_scale8.log; fi
   for n in 1 2 4 8; do
     [ "$n" -gt "$NG" ] && break
-    timeout 900 python bench.py --gpus $n --frames 124 --steps 2 --warmup 1 --no-cpu-baseline --detail $OUT/${T}_scale_${n}_detail.json \
+    timeout 900 python bench.py --full --gpus $n --frames 124 --steps 2 --warmup 1 --no-cpu-baseline --detail $OUT/${T}_scale_${n}_detail.json \
       > $OUT/${T}_scale_${n}.json 2> $OUT/${T}_scale_${n}.err
     echo "N=$n: exit $? $(fps_of < $OUT/${T}_scale_${n}.json)" | tee -a $OUT/${T}_scale8.log
   done ;;
