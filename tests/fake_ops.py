@@ -1,10 +1,11 @@
-"""Torch/CPU stand-ins for a few `v_express_amd.ops` entry points — TEST INFRASTRUCTURE for the CPU suite only.
+"""Torch stand-ins for the `v_express_amd.ops` entry points — TEST INFRASTRUCTURE.
 
 They let the *host composition* of a model (weight re-layouts, strided window views, buffer plumbing, call order) be
 checked against the oracle in the dev container, where no GPU exists.  Same signatures and output dtypes (bf16 rounding
 at every kernel boundary) as the real wrappers; the arithmetic inside is float64 torch, so - like the real kernels - a
 row's result does not depend on how many other rows share the call (fp32 BLAS blocking would).  Never imported by the
-package; the GPU tests run the same model code on the real kernels.
+package.  Every restatement also runs on device tensors without host round trips: tests/census.py checks each launch
+of a full-size clip against them on the GPU.
 """
 import torch
 import torch.nn.functional as F
@@ -79,7 +80,7 @@ def layernorm(x, gamma, beta, eps=1e-5, *, add=None, add_rows_per_entry=1, add_e
     x2 = x.reshape(-1, x.shape[-1]) if x.is_contiguous() else x
     y = F.layer_norm(x2.double(), (x2.shape[-1],), gamma.double(), beta.double(), eps)
     if add is not None:
-        idx = (torch.arange(y.shape[0]) // add_rows_per_entry) % add_entries
+        idx = (torch.arange(y.shape[0], device=y.device) // add_rows_per_entry) % add_entries
         y = y + add.double().reshape(-1, y.shape[-1])[idx]
     y = y.to(BF16)
     if out is not None:
@@ -128,13 +129,13 @@ def layernorm_fp8(x, gamma, beta, eps=1e-5, *, add=None, add_rows_per_entry=1, a
     if gamma is not None:
         y = F.layer_norm(y, (y.shape[-1],), gamma.double(), beta.double(), eps)
         if add is not None:
-            idx = (torch.arange(y.shape[0]) // add_rows_per_entry) % add_entries
+            idx = (torch.arange(y.shape[0], device=y.device) // add_rows_per_entry) % add_entries
             y = y + add.double().reshape(-1, y.shape[-1])[idx]
     y = y.float()
     amax = y.abs().amax(dim=1)
     sc = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
     k = y.shape[1]
-    q = torch.zeros((y.shape[0], real_ops.pad128(k)), dtype=torch.uint8)
+    q = torch.zeros((y.shape[0], real_ops.pad128(k)), dtype=torch.uint8, device=y.device)
     q[:, :k] = (y / sc[:, None]).to(torch.float8_e4m3fn).view(torch.uint8)
     return real_ops.Fp8Rows(q, sc, k)
 
@@ -201,7 +202,7 @@ def gemm(a, w, bias=None, *, geom=None, a2=None, residual=None, alpha=1.0, act=0
         y = y + bias
     if rowbias is not None:
         assert rowbias.dtype == torch.float32 and rows_per_group > 0
-        grp = torch.arange(y.shape[0]) // rows_per_group
+        grp = torch.arange(y.shape[0], device=y.device) // rows_per_group
         y = y + rowbias[grp, :y.shape[1]]
     y = _act(y, act)
     # the accumulator + bias is a float32 value in the kernel; the residual is added to it in float32, then ONE rounding to
@@ -285,15 +286,31 @@ def key_norm_max(k, *, kv_batches, heads, n_kv, head_dim):
         kv_batches, n_kv, heads, head_dim).norm(dim=-1).amax(dim=1).reshape(-1).float()
 
 
+_SCORES = 1 << 27
+
+
 def attention(q, k, vt, *, batch, heads, n_q, n_kv, head_dim, q_per_kv=1, out=None, kmax=None, k_prescaled=False):
     c = heads * head_dim
     kvb = batch // q_per_kv
-    qh = q.double().reshape(batch, n_q, heads, head_dim).transpose(1, 2)
-    kh = k.double().reshape(kvb, n_kv, heads, head_dim).transpose(1, 2).repeat_interleave(q_per_kv, dim=0)
-    if k_prescaled:      # k carries d^-1/2 log2(e): softmax_j 2^(q.k_j)  ==  SDPA on k * sqrt(d) * ln 2
-        kh = kh * (head_dim ** 0.5 * 0.6931471805599453)
-    vh = vt[..., :n_kv].double().transpose(-1, -2).repeat_interleave(q_per_kv, dim=0)
-    o = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(batch * n_q, c).to(BF16)
+    q4 = q.reshape(batch, n_q, -1)[..., :c]
+    k4 = k.reshape(kvb, n_kv, -1)[..., :c]
+    o = torch.empty((batch, n_q, c), dtype=BF16, device=q.device)
+    # float64 scores of at most ~_SCORES elements at a time (32 x 8 x 4096 x 8192 of them at the 64x64 level): chunks of
+    # whole batch items, or of query rows when one item is larger; a row's result does not depend on the chunking
+    nb = max(1, min(batch, _SCORES // (heads * n_q * n_kv)))
+    nq = n_q if nb > 1 or heads * n_q * n_kv <= _SCORES else max(1, _SCORES // (heads * n_kv))
+    for b0 in range(0, batch, nb):
+        b1 = min(batch, b0 + nb)
+        kv_ids = torch.arange(b0, b1, device=q.device) // q_per_kv
+        kh = k4.index_select(0, kv_ids).double().reshape(b1 - b0, n_kv, heads, head_dim).transpose(1, 2)
+        if k_prescaled:      # k carries d^-1/2 log2(e): softmax_j 2^(q.k_j)  ==  SDPA on k * sqrt(d) * ln 2
+            kh = kh * (head_dim ** 0.5 * 0.6931471805599453)
+        vh = vt.index_select(0, kv_ids)[..., :n_kv].double().transpose(-1, -2)
+        for q0 in range(0, n_q, nq):
+            q1 = min(n_q, q0 + nq)
+            qh = q4[b0:b1, q0:q1].double().reshape(b1 - b0, q1 - q0, heads, head_dim).transpose(1, 2)
+            o[b0:b1, q0:q1] = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(b1 - b0, q1 - q0, c)
+    o = o.reshape(batch * n_q, c)
     if out is not None:
         out.copy_(o)
         return out
@@ -339,7 +356,7 @@ def audio_xattn_pack(kv, wq_folded, bq_folded, wo, *, frames, n_ctx, heads):
     wq = wq_folded.double().reshape(heads, d, c)                        # rows h d + j
     kq = (torch.einsum("fthj,hjc->fhtc", k, wq) * scale).to(BF16)
     colsum = kq.double().sum(-1)
-    sbias = torch.zeros(frames, heads, n_ctx, dtype=torch.float64)
+    sbias = torch.zeros(frames, heads, n_ctx, dtype=torch.float64, device=kv.device)
     if bq_folded is not None:
         sbias = torch.einsum("fthj,hj->fht", k, bq_folded.double().reshape(heads, d)) * scale
     wo_h = wo.double().reshape(c, heads, d)
@@ -376,7 +393,7 @@ def upsample_conv_phases(x, w_phases, bias, *, frames, H, W):
     rounding per phase output) interleaved into the 2H x 2W image."""
     cin, cout = x.shape[-1], w_phases.shape[1]
     xp = F.pad(x.double().reshape(frames, H, W, cin).permute(0, 3, 1, 2), (1, 1, 1, 1))
-    out = torch.empty((frames, 2 * H, 2 * W, cout), dtype=BF16)
+    out = torch.empty((frames, 2 * H, 2 * W, cout), dtype=BF16, device=x.device)
     for a in (0, 1):
         for b in (0, 1):
             w = w_phases[a * 2 + b].double().reshape(cout, 2, 2, cin).permute(0, 3, 1, 2)
@@ -403,7 +420,7 @@ def add_row_bias(x, bias, alpha=1.0):
 def gather_latents(latents, frame_ids, reps, c_pad=8):
     _, c, _, h, w = latents.shape
     x = latents[0][:, frame_ids.long()].reshape(c, -1, h * w).permute(1, 2, 0)            # [f, hw, C]
-    out = torch.zeros((reps, x.shape[0], h * w, c_pad), dtype=BF16)
+    out = torch.zeros((reps, x.shape[0], h * w, c_pad), dtype=BF16, device=latents.device)
     out[..., :c] = x.to(BF16)
     return out.reshape(reps * x.shape[0], h * w, c_pad)
 
@@ -421,34 +438,31 @@ def combine_units(gathered, unit_index, c, f, hw, guidance, preds):
     nW, halves, S = unit_index.shape
     f_loc = f // S
     g = gathered.reshape(-1, f_loc * hw, c)
-    for wi in range(nW):
-        h = [torch.cat([g[int(unit_index[wi, hh, j])] for j in range(S)], dim=0) for hh in range(halves)]   # [f*hw, c]
-        u, cnd = h[0].double(), h[-1].double()
-        r = u + guidance * (cnd - u)
-        preds[wi].copy_(r.view(f, hw, c).permute(2, 0, 1))
+    h = g.index_select(0, unit_index.reshape(-1).long()).view(nW, halves, f * hw, c)      # granules j = 0..S-1 in order
+    u, cnd = h[:, 0].double(), h[:, -1].double()
+    r = u + guidance * (cnd - u)
+    preds.copy_(r.view(nW, f, hw, c).permute(0, 3, 1, 2))
 
 
 def overlap_ddim_step(latents, preds, terms, frame_ids, counts, coef):
     sa, s1a, sap, s1ap = (float(v) for v in coef)
     _, c, _, h, w = latents.shape
-    new = {}
-    for i, fr in enumerate(frame_ids.tolist()):
-        v = None
-        for slot, li in terms[i].tolist():
-            if slot < 0:
-                continue
-            term = preds[slot, :, li] / counts[i]
-            v = term if v is None else v + term
-        x = latents[0, :, fr].reshape(c, h * w)
-        new[fr] = (sap * (sa * x - s1a * v) + s1ap * (sa * v + s1a * x)).reshape(c, h, w)
-    for fr, val in new.items():
-        latents[0, :, fr] = val
+    fr = frame_ids.long()
+    v = None
+    for j in range(terms.shape[1]):            # the terms of a frame in order (unused slots, -1, trail: + 0 changes nothing)
+        slot, li = terms[:, j, 0].long(), terms[:, j, 1].long()
+        term = preds[slot.clamp_min(0), :, li.clamp_min(0)] / counts[:, None, None]                  # [frames, c, hw]
+        term = torch.where((slot >= 0)[:, None, None], term, torch.zeros_like(term))
+        v = term if v is None else v + term
+    x = latents[0].index_select(1, fr).transpose(0, 1).reshape(-1, c, h * w)
+    new = sap * (sa * x - s1a * v) + s1ap * (sa * v + s1a * x)
+    latents[0].index_copy_(1, fr, new.reshape(-1, c, h, w).transpose(0, 1))
 
 
 def ncfhw_to_nhwc(x, c_pad=None):
     b, c, f, h, w = x.shape
     c_pad = c_pad or (c + 7) // 8 * 8
-    out = torch.zeros((b * f, h * w, c_pad), dtype=BF16)
+    out = torch.zeros((b * f, h * w, c_pad), dtype=BF16, device=x.device)
     out[..., :c] = x.double().permute(0, 2, 3, 4, 1).reshape(b * f, h * w, c).to(BF16)
     return out
 
