@@ -424,6 +424,14 @@ int vx_combine_units(const float* gathered, const int32_t* unit_index, int n_win
 int vx_overlap_ddim_step(float* latents, int c, int total_frames, int hw, const float* preds, int f_window,
                          const int32_t* terms, int max_terms, const int32_t* frame_ids, const float* count,
                          int n_frames, float sqrt_a, float sqrt_1ma, float sqrt_ap, float sqrt_1map, void* stream);
+/* per-frame mean-overlap + DPM-Solver++ multistep update (v-prediction, data prediction, midpoint): v summed exactly as
+ * in vx_overlap_ddim_step; x0 = alpha_s x - sigma_s v; latents[:, :, frame] = c_x x - c_0 x0 + c_1 x0_prev.
+ * x0_history: float32 laid out like latents, read when c_1 != 0 and overwritten with this step's x0.  The host
+ * collapses first- and second-order updates to (c_x, c_0, c_1) (scheduler.DPMSolverMultistepScheduler).  */
+int vx_overlap_multistep_step(float* latents, int c, int total_frames, int hw, const float* preds, int f_window,
+                              const int32_t* terms, int max_terms, const int32_t* frame_ids, const float* count,
+                              int n_frames, float* x0_history, float alpha_s, float sigma_s, float c_x, float c_0,
+                              float c_1, void* stream);
 /* NCHW-ish float32 [b, C, f, h, w] -> NHWC bf16 [(b f), h*w, c_pad]  (API-boundary layout change) */
 int vx_ncfhw_to_nhwc(const float* x, int b, int c, int f, int hw, int c_pad, void* out, void* stream);
 /* NHWC float32 [(b f), hw, ld] -> [b, C, f, h*w] float32 */

@@ -1,0 +1,39 @@
+"""One rank of tests/test_dpm_solver_cpu.py's two-rank gloo run (TEST INFRASTRUCTURE): the small-config denoising loop
+with a DPM-Solver++ scheduler under emulated kernels (tests/fake_ops.py + dpm_restated.overlap_multistep_step)."""
+import os
+import sys
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+
+import cases  # noqa: E402
+import dist_gpu_worker as W  # noqa: E402
+import dpm_restated as D  # noqa: E402
+
+# F = 14 in windows of 8 with overlap 2 (two windows, four CFG units), 3 DPM++ 2M steps (orders 1, 2, 1), 8x8 latents
+F, CF, CO, STEPS, LATENT = 14, 8, 2, 3, 8
+
+
+def run():
+    from v_express_amd import DPMSolverMultistepScheduler
+    pipe = W.build_pipeline("cpu")
+    pipe.scheduler = DPMSolverMultistepScheduler(**D.KWARGS)
+    return W._run(pipe, pipe.denoising_unet, pipe.reference_net, pipe.scheduler, cases.unet_cfg(cases.SMALL), F, CF,
+                  CO, STEPS, 0, LATENT, "cpu")
+
+
+def main():
+    """Under RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT: this rank's final latents."""
+    import torch.distributed as dist
+    from v_express_amd import ops
+    torch.set_num_threads(2)
+    dist.init_process_group("gloo")
+    W.emulate_kernels()
+    ops.overlap_multistep_step = D.overlap_multistep_step
+    lat = run()
+    dist.barrier()
+    dist.destroy_process_group()
+    return lat

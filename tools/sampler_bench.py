@@ -1,0 +1,116 @@
+"""Time one BASELINE configs[1] clip (512x512, F = 16 in one window, CFG 3.5, synthetic weights, the set-up of bench.py)
+with a chosen sampler and step count (GPU box):
+    python tools/sampler_bench.py --scheduler ddim --steps 25
+    python tools/sampler_bench.py --scheduler dpm --steps 15 [--order 2]
+Prints one JSON line: ms per clip (host clock around whole clips, ending in a device synchronise), the denoise and decode
+milliseconds of the same clips (HIP events), and the average microseconds of the per-step update launch (HIP events
+around each `ops.overlap_ddim_step` / `ops.overlap_multistep_step` of one further, instrumented clip)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scheduler", choices=("ddim", "dpm"), default="ddim")
+    ap.add_argument("--steps", type=int, default=25)
+    ap.add_argument("--order", type=int, choices=(1, 2), default=2, help="DPM-Solver++ solver_order")
+    ap.add_argument("--clips", type=int, default=5, help="timed clips")
+    ap.add_argument("--warmup", type=int, default=1)
+    args = ap.parse_args()
+    if args.steps < 1 or args.clips < 1:
+        ap.error("--steps and --clips must be >= 1")
+    if not torch.cuda.is_available():
+        raise SystemExit("sampler_bench.py measures on the GPU: no device visible")
+    import v_express_amd as vx
+    from v_express_amd import ops, synth
+    from v_express_amd.context import uniform
+    dev, elem = torch.device("cuda", 0), torch.bfloat16
+    torch.cuda.set_device(dev)
+    cfg, vcfg = synth.UNetConfig(), synth.VaeConfig()
+    F, h = 16, 64
+    unet = vx.UNet3DConditionModel(cfg).to(dev).to(elem)
+    refnet = vx.UNet2DConditionModel(cfg).to(dev).to(elem)
+    vae = vx.AutoencoderKLDecoder(vcfg).to(dev).to(elem)
+    unet.load_state_dict(synth.unet3d_state_dict(cfg, seed=42, device=dev, dtype=elem, draw_on_device=True))
+    unet.release_raw_weights()
+    refnet.load_state_dict(synth.refnet_state_dict(cfg, seed=43, device=dev, dtype=elem, draw_on_device=True))
+    refnet.release_raw_weights()
+    vae.load_state_dict(synth.vae_decoder_state_dict(vcfg, seed=44, device=dev, dtype=elem, draw_on_device=True))
+    vae._prepared()
+    kw = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", clip_sample=False, steps_offset=1,
+              prediction_type="v_prediction", rescale_betas_zero_snr=True, timestep_spacing="trailing")
+    if args.scheduler == "ddim":
+        sched, update = vx.DDIMScheduler(**kw), "overlap_ddim_step"
+    else:
+        sched, update = vx.DPMSolverMultistepScheduler(**kw, solver_order=args.order), "overlap_multistep_step"
+    pipe = vx.VExpressPipeline(vae=vae, reference_net=refnet, denoising_unet=unet, scheduler=sched)
+    inp = synth.synthetic_inputs(cfg, F, h, h, seed=42, device=dev)
+    writer = vx.ReferenceAttentionControl(refnet, do_classifier_free_guidance=True, mode="write", fusion_blocks="full")
+    reader = vx.ReferenceAttentionControl(unet, do_classifier_free_guidance=True, mode="read", fusion_blocks="full",
+                                          reference_attention_weight=0.95, audio_attention_weight=3.0)
+    refnet(inp["ref_latents"], timestep=0, encoder_hidden_states=torch.zeros(1, 1, 768, device=dev), return_dict=False)
+    reader.update(writer, True)
+    sched.set_timesteps(args.steps)
+    timesteps = sched.timesteps.tolist()
+    windows = list(uniform(step=0, num_frames=F, context_size=16, context_stride=1, context_overlap=4,
+                           closed_loop=False))
+    c0 = cfg.block_out_channels[0]
+    kps_tokens = ops.ncfhw_to_nhwc(inp["kps_features"], c0).view(2, F, h * h, c0)
+    audio = inp["audio_embeddings"].to(elem).contiguous()
+
+    def one_clip(ev=None):
+        lat = inp["latents"].clone()
+        if ev:
+            ev[0].record()
+        pipe.denoise(lat, kps_tokens, audio, timesteps, windows, 3.5)
+        if ev:
+            ev[1].record()
+        video = pipe.decode_latents(lat)
+        if ev:
+            ev[2].record()
+        return video
+
+    for _ in range(args.warmup):
+        one_clip()
+    torch.cuda.synchronize()
+    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.clips)]
+    t0 = time.perf_counter()
+    for ev in evs:
+        video = one_clip(ev)
+    torch.cuda.synchronize()
+    clip_ms = 1e3 * (time.perf_counter() - t0) / args.clips
+    denoise_ms = sum(e[0].elapsed_time(e[1]) for e in evs) / args.clips
+    decode_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / args.clips
+    assert video.shape == (1, 3, F, 512, 512) and torch.isfinite(video).all()
+    # one more clip with events around every update launch (kept out of the timed clips above)
+    orig, marks = getattr(ops, update), []
+
+    def marked(*a, **k):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        orig(*a, **k)
+        e.record()
+        marks.append((s, e))
+    setattr(ops, update, marked)
+    try:
+        one_clip()
+    finally:
+        setattr(ops, update, orig)
+    torch.cuda.synchronize()
+    update_us = 1e3 * sum(s.elapsed_time(e) for s, e in marks) / len(marks)
+    print(json.dumps(dict(
+        scheduler=args.scheduler, order=args.order if args.scheduler == "dpm" else None, steps=args.steps,
+        config="512x512, 16 frames (one window), CFG 3.5, synthetic weights, bf16", clips=args.clips,
+        ms_per_clip=round(clip_ms, 2), denoise_ms=round(denoise_ms, 2), decode_ms=round(decode_ms, 2),
+        frames_per_s=round(F * 1e3 / clip_ms, 3), update_launches=len(marks), update_us=round(update_us, 2))))
+
+
+if __name__ == "__main__":
+    main()

@@ -155,6 +155,41 @@ __global__ void overlap_ddim_kernel(float* latents, int c, int total_frames, int
   *lp = sqrt_ap * x0 + sqrt_1map * eps;
 }
 
+// One DPM-Solver++ multistep update per frame (v-prediction, data prediction): the averaged v exactly as
+// overlap_ddim_kernel sums it, x0 = alpha_s x - sigma_s v, x' = c_x x - c_0 x0 + c_1 x0_prev.  x0_history (fp32, laid
+// out like latents) holds the previous step's x0: read only when c_1 != 0 (the first step finds it unwritten), then
+// overwritten with this step's x0.
+__global__ void overlap_multistep_kernel(float* latents, int c, int total_frames, int hw, const float* preds,
+                                         int f_window, const int32_t* terms, int max_terms, const int32_t* frame_ids,
+                                         const float* count, int n_frames, float* x0_history, float alpha_s,
+                                         float sigma_s, float c_x, float c_0, float c_1) {
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // (frame slot, channel, pixel)
+  long total = (long)n_frames * c * hw;
+  if (idx >= total) return;
+  int px = (int)(idx % hw);
+  int ch = (int)((idx / hw) % c);
+  int fs = (int)(idx / ((long)hw * c));
+  int fr = frame_ids[fs];
+  float ic = count[fs];
+  float v = 0.f;
+  bool first = true;
+  for (int t = 0; t < max_terms; ++t) {
+    int slot = terms[(fs * max_terms + t) * 2 + 0];
+    int li = terms[(fs * max_terms + t) * 2 + 1];
+    if (slot < 0) continue;
+    float term = preds[(((size_t)slot * c + ch) * f_window + li) * hw + px] / ic;
+    v = first ? term : v + term;
+    first = false;
+  }
+  size_t off = ((size_t)ch * total_frames + fr) * hw + px;
+  float x = latents[off];
+  float x0 = alpha_s * x - sigma_s * v;
+  float out = c_x * x - c_0 * x0;
+  if (c_1 != 0.f) out += c_1 * x0_history[off];
+  x0_history[off] = x0;
+  latents[off] = out;
+}
+
 // x fp32 [b, c, f, hw] -> out bf16 [(b f), hw, c_pad]; LDS transpose so both sides are coalesced for wide c
 __global__ void ncfhw_to_nhwc_kernel(const float* x, int b, int c, int f, int hw, int c_pad, bf16_t* out) {
   __shared__ float tile[32][33];
@@ -354,6 +389,18 @@ extern "C" int vx_overlap_ddim_step(float* latents, int c, int total_frames, int
                      c, total_frames, hw, preds, f_window, terms, max_terms, frame_ids, count, n_frames, sqrt_a,
                      sqrt_1ma, sqrt_ap, sqrt_1map);
   return vx_check_launch("vx_overlap_ddim_step");
+}
+
+extern "C" int vx_overlap_multistep_step(float* latents, int c, int total_frames, int hw, const float* preds,
+                                         int f_window, const int32_t* terms, int max_terms, const int32_t* frame_ids,
+                                         const float* count, int n_frames, float* x0_history, float alpha_s,
+                                         float sigma_s, float c_x, float c_0, float c_1, void* stream) {
+  VX_REQUIRE(latents && preds && terms && frame_ids && count && x0_history && n_frames > 0 && max_terms > 0,
+             "vx_overlap_multistep_step: bad arguments");
+  hipLaunchKernelGGL(overlap_multistep_kernel, grid1d((long)n_frames * c * hw), dim3(256), 0, (hipStream_t)stream,
+                     latents, c, total_frames, hw, preds, f_window, terms, max_terms, frame_ids, count, n_frames,
+                     x0_history, alpha_s, sigma_s, c_x, c_0, c_1);
+  return vx_check_launch("vx_overlap_multistep_step");
 }
 
 extern "C" int vx_ncfhw_to_nhwc(const float* x, int b, int c, int f, int hw, int c_pad, void* out, void* stream) {

@@ -160,6 +160,8 @@ def _load(path=None, element="bf16"):
     lib.vx_pack_rows.argtypes = [vp, i32, i64, i32, vp, vp]
     lib.vx_combine_units.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp]
     lib.vx_overlap_ddim_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, f32, f32, f32, f32, vp]
+    lib.vx_overlap_multistep_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, f32, f32, f32, f32,
+                                              f32, vp]
     lib.vx_ncfhw_to_nhwc.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
     lib.vx_nhwc_to_ncfhw.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
     lib.vx_vae_postprocess.argtypes = [vp, i32, i32, i32, i32, vp, vp]

@@ -1342,6 +1342,19 @@ def overlap_ddim_step(latents, preds, terms, frame_ids, counts, coef):
                                       _stream()), "vx_overlap_ddim_step")
 
 
+def overlap_multistep_step(latents, preds, terms, frame_ids, counts, x0_history, coef):
+    """DPM-Solver++ update of `frame_ids`: latents fp32 [1,C,F,h,w] updated in place, preds fp32 [slots, C, f, hw];
+    x0_history fp32 shaped like latents (read when coef's c_1 != 0, then overwritten with this step's x0);
+    coef = (alpha, sigma, c_x, c_0, c_1) of DPMSolverMultistepScheduler.multistep_coefficients."""
+    if x0_history.dtype != torch.float32 or x0_history.shape != latents.shape or not x0_history.is_contiguous():
+        raise TypeError("overlap_multistep_step: x0_history must be contiguous float32 of the latents' shape")
+    _, c, F, h, w = latents.shape
+    n = frame_ids.numel()
+    L.check(_lib.vx_overlap_multistep_step(_ptr(latents), c, F, h * w, _ptr(preds), preds.shape[2], _ptr(terms),
+                                           terms.shape[1], _ptr(frame_ids), _ptr(counts), n, _ptr(x0_history),
+                                           *[float(v) for v in coef], _stream()), "vx_overlap_multistep_step")
+
+
 def ncfhw_to_nhwc(x, c_pad=None):
     """fp32 [b, C, f, h, w] -> bf16 [(b f), h*w, c_pad]."""
     b, c, f, h, w = x.shape

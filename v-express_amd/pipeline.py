@@ -29,6 +29,7 @@ from .context import get_context_scheduler, overlap_plan
 from .distributed import (DistContext, MixedUnitSchedule, UnitSchedule, choose_frame_shards, choose_mixed_shards,
                           split_frames)
 from .mutual_self_attention import ReferenceAttentionControl
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler
 
 
 def _in_unet_element_type(fn):
@@ -193,12 +194,31 @@ class VExpressPipeline:
         return latents.to(device=device, dtype=torch.float32) * self.scheduler.init_noise_sigma
 
     # ------------------------------------------------------------------ the hot loop
+    def _multistep(self):
+        """False: DDIM (vx_overlap_ddim_step); True: DPM-Solver++ (vx_overlap_multistep_step).  Any other scheduler raises
+        TypeError before anything runs: the fused updates are the only ones the loop has."""
+        if isinstance(self.scheduler, DDIMScheduler):
+            return False
+        if isinstance(self.scheduler, DPMSolverMultistepScheduler):
+            return True
+        raise TypeError(f"the denoising loop drives v_express_amd.DDIMScheduler or "
+                        f"v_express_amd.DPMSolverMultistepScheduler, not {type(self.scheduler).__name__}")
+
     @_in_unet_element_type
     def denoise(self, latents, kps_tokens, audio, timesteps, windows, guidance_scale, callback=None,
-                callback_steps=1):
+                callback_steps=1, *, begin_index=None):
         """pipelines/v_express_pipeline.py:526-583.  latents fp32 [1,4,F,h,w] (device, updated in place);
         kps_tokens bf16 [b, F, hw, C0]; audio bf16 [b, F, n_ctx, 768] with b = 2 (uncond, cond) under classifier-free
-        guidance (guidance_scale > 1, :443) and b = 1 (the conditional row only) without."""
+        guidance (guidance_scale > 1, :443) and b = 1 (the conditional row only) without.
+        DPM-Solver++: `timesteps` are the scheduler's from step index `begin_index` on (default: its last
+        len(timesteps)); each frame gets exactly one update per timestep, so the multistep history is per frame."""
+        multistep = self._multistep()
+        if multistep:
+            all_ts = self.scheduler.timesteps.tolist()
+            if begin_index is None:
+                begin_index = len(all_ts) - len(timesteps)
+            if [int(t) for t in timesteps] != all_ts[begin_index:begin_index + len(timesteps)]:
+                raise ValueError("DPM-Solver++: timesteps must be the scheduler's own, from step index begin_index on")
         unet, dc, dev = self.denoising_unet, self.dist, latents.device
         _, C, F, H, W = latents.shape
         hw = H * W
@@ -303,6 +323,11 @@ class VExpressPipeline:
                 n_slots = len(rows) * (G // Sc)
                 # the audio K | V of all 16 transformer blocks is step-invariant: once per clip and call
                 calls.append((rows, gathers, kps, ehs, unet.precompute_audio_kv(ehs), f_loc, shard, s0, n_slots))
+        # DPM-Solver++: the previous step's x0 of every frame (identical on every rank, like the latents) and the
+        # update coefficients of every step, resolved on the host before the loop
+        x0_hist = torch.empty_like(latents) if multistep else None
+        coefs = [self.scheduler.multistep_coefficients(begin_index + i, begin_index)
+                 for i in range(len(timesteps))] if multistep else None
         for i, t in enumerate(timesteps):
             t = int(t)
             for rows, gathers, kps, ehs, akv, f_loc, shard, s0, n_slots in calls:
@@ -316,7 +341,10 @@ class VExpressPipeline:
             gathered = dc.all_gather_units(local, max_slots)          # [world, max_slots, (f/G)*hw, C]
             # CFG combine of every window in one launch (:548-550; without CFG the prediction itself)
             ops.combine_units(gathered, uidx, C, f, hw, guidance_scale if do_cfg else 1.0, preds)
-            ops.overlap_ddim_step(latents, preds, terms, frame_ids, counts, self.scheduler.step_coefficients(t))
+            if multistep:
+                ops.overlap_multistep_step(latents, preds, terms, frame_ids, counts, x0_hist, coefs[i])
+            else:
+                ops.overlap_ddim_step(latents, preds, terms, frame_ids, counts, self.scheduler.step_coefficients(t))
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, latents)
         return latents
@@ -355,12 +383,14 @@ class VExpressPipeline:
                  output_device="cpu", decode=True, **kwargs):
         if eta != 0.0:
             raise NotImplementedError("eta != 0 is unused by V-Express")
+        self._multistep()                      # an unsupported scheduler fails here, before the prologue
         dev = self.device
         do_cfg = guidance_scale > 1.0
         # timesteps (retrieve_timesteps + get_timesteps, :448-449)
         self.scheduler.set_timesteps(num_inference_steps)
         init_t = min(int(num_inference_steps * strength), num_inference_steps)
-        timesteps = self.scheduler.timesteps[max(num_inference_steps - init_t, 0):].tolist()
+        begin_index = max(num_inference_steps - init_t, 0)
+        timesteps = self.scheduler.timesteps[begin_index:].tolist()
         writer = ReferenceAttentionControl(self.reference_net, do_classifier_free_guidance=do_cfg, mode="write",
                                            batch_size=1, fusion_blocks="full")
         reader = ReferenceAttentionControl(self.denoising_unet, do_classifier_free_guidance=do_cfg, mode="read",
@@ -399,7 +429,8 @@ class VExpressPipeline:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed else None
         if timed:
             ev[0].record()
-        self.denoise(lat, kps_tokens, audio, timesteps, windows, guidance_scale, callback, callback_steps or 1)
+        self.denoise(lat, kps_tokens, audio, timesteps, windows, guidance_scale, callback, callback_steps or 1,
+                     begin_index=begin_index)
         if timed:
             ev[1].record()
         reader.clear()

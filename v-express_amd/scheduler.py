@@ -1,15 +1,36 @@
-"""DDIM scheduler with the configuration the reference builds (inference.py:132-136 from
+"""DDIM and DPM-Solver++ schedulers.  DDIM has the configuration the reference builds (inference.py:132-136 from
 inference_v2.yaml:24-35): scaled-linear betas rescaled to zero terminal SNR, trailing timestep spacing,
 v-prediction, eta = 0.  The arithmetic is diffusers==0.29.2 `DDIMScheduler` (absent third-party dependency;
 restated from its published behaviour — SURVEY.md Appendix A).
 
 Host side only: the per-step update itself runs in the fused `vx_overlap_ddim_step` kernel, fed by
-`step_coefficients(t)`; `step()` is kept as the reference-compatible tensor API.
+`step_coefficients(t)`; `step()` is kept as the reference-compatible tensor API.  DPMSolverMultistepScheduler (the
+second-order multistep sampler of the reference's scheduler list, pipelines/v_express_pipeline.py:83-90) feeds
+`vx_overlap_multistep_step` the same way through `multistep_coefficients(i)`.
 """
 from types import SimpleNamespace
 
+import math
+
 import numpy as np
 import torch
+
+
+def _betas(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr):
+    """float32 beta table of diffusers' schedulers: linear or scaled-linear, optionally rescaled to zero terminal SNR."""
+    if beta_schedule == "linear":
+        betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+    elif beta_schedule == "scaled_linear":
+        betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+    else:
+        raise NotImplementedError(beta_schedule)
+    if rescale_betas_zero_snr:
+        abar_sqrt = torch.cumprod(1.0 - betas, 0).sqrt()
+        a0, aT = abar_sqrt[0].clone(), abar_sqrt[-1].clone()
+        abar_sqrt = (abar_sqrt - aT) * (a0 / (a0 - aT))
+        abar = abar_sqrt ** 2
+        betas = 1 - torch.cat([abar[0:1], abar[1:] / abar[:-1]])
+    return betas
 
 
 class DDIMScheduler:
@@ -18,24 +39,15 @@ class DDIMScheduler:
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                  clip_sample=True, set_alpha_to_one=True, steps_offset=0, prediction_type="epsilon",
                  timestep_spacing="leading", rescale_betas_zero_snr=False, **unused):
-        if beta_schedule == "linear":
-            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
-        elif beta_schedule == "scaled_linear":
-            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
-        else:
-            raise NotImplementedError(beta_schedule)
-        if rescale_betas_zero_snr:
-            abar_sqrt = torch.cumprod(1.0 - betas, 0).sqrt()
-            a0, aT = abar_sqrt[0].clone(), abar_sqrt[-1].clone()
-            abar_sqrt = (abar_sqrt - aT) * (a0 / (a0 - aT))
-            abar = abar_sqrt ** 2
-            betas = 1 - torch.cat([abar[0:1], abar[1:] / abar[:-1]])
+        betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
         self.betas = betas
         self.alphas_cumprod = torch.cumprod(1.0 - betas, 0)
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, clip_sample=clip_sample,
                                       steps_offset=steps_offset, prediction_type=prediction_type,
-                                      timestep_spacing=timestep_spacing)
+                                      timestep_spacing=timestep_spacing, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, set_alpha_to_one=set_alpha_to_one,
+                                      rescale_betas_zero_snr=rescale_betas_zero_snr)
         if clip_sample:
             raise NotImplementedError("clip_sample=True is not used by V-Express (inference_v2.yaml:28)")
         if prediction_type != "v_prediction":
@@ -81,3 +93,138 @@ class DDIMScheduler:
         x0 = sa * sample - s1a * model_output
         eps = sa * model_output + s1a * sample
         return SimpleNamespace(prev_sample=sap * x0 + s1ap * eps, pred_original_sample=x0)
+
+
+class DPMSolverMultistepScheduler:
+    """DPM-Solver++ (multistep, data prediction, midpoint) for the zero-terminal-SNR v-prediction schedule: the arithmetic
+    of diffusers==0.29.2 `DPMSolverMultistepScheduler` restated for the options listed in `__init__` (any other value
+    raises NotImplementedError naming the option).
+
+    The loop runs the update in the fused `vx_overlap_multistep_step` kernel, fed by `multistep_coefficients(i)`:
+        x0 = alpha_i x - sigma_i v ;   x' = c_x x - c_0 x0 + c_1 x0_prev
+    with the previous step's x0 kept on the device.  `step()` is the stateful diffusers-style tensor API.
+    """
+    order = 1
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False,
+                 dynamic_thresholding_ratio=0.995, sample_max_value=1.0, algorithm_type="dpmsolver++",
+                 solver_type="midpoint", lower_order_final=True, euler_at_final=False, use_karras_sigmas=False,
+                 use_lu_lambdas=False, final_sigmas_type="zero", lambda_min_clipped=-float("inf"),
+                 variance_type=None, timestep_spacing="linspace", steps_offset=0, rescale_betas_zero_snr=False,
+                 **unused):
+        # (clip_sample, set_alpha_to_one, ... of a DDIM configuration are not parameters of this solver: ignored, as
+        # diffusers' from_config does)
+        for name, value, ok in (("trained_betas", trained_betas, trained_betas is None),
+                                ("solver_order", solver_order, solver_order in (1, 2)),
+                                ("prediction_type", prediction_type, prediction_type == "v_prediction"),
+                                ("thresholding", thresholding, not thresholding),
+                                ("algorithm_type", algorithm_type, algorithm_type == "dpmsolver++"),
+                                ("solver_type", solver_type, solver_type == "midpoint"),
+                                ("use_karras_sigmas", use_karras_sigmas, not use_karras_sigmas),
+                                ("use_lu_lambdas", use_lu_lambdas, not use_lu_lambdas),
+                                ("final_sigmas_type", final_sigmas_type, final_sigmas_type in ("zero", "sigma_min")),
+                                ("lambda_min_clipped", lambda_min_clipped, lambda_min_clipped == -float("inf")),
+                                ("variance_type", variance_type, variance_type is None),
+                                ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing")):
+            if not ok:
+                raise NotImplementedError(f"DPMSolverMultistepScheduler: {name}={value!r} is not built")
+        self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
+        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, 0)
+        if rescale_betas_zero_snr:
+            # the zero-SNR table ends at alphas_cumprod = 0: diffusers clamps it so that the first sigma is finite
+            self.alphas_cumprod[-1] = 2 ** -24
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, solver_order=solver_order,
+                                      prediction_type=prediction_type, algorithm_type=algorithm_type,
+                                      solver_type=solver_type, lower_order_final=lower_order_final,
+                                      euler_at_final=euler_at_final, final_sigmas_type=final_sigmas_type,
+                                      timestep_spacing=timestep_spacing, steps_offset=steps_offset,
+                                      rescale_betas_zero_snr=rescale_betas_zero_snr)
+        # sigma(t) = sqrt((1 - abar_t) / abar_t) in float32, as diffusers computes it
+        self.sigma_table = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
+        self.init_noise_sigma = 1.0
+        self.num_inference_steps = None
+        self.timesteps = None
+        self.sigmas = None
+        self._reset()
+
+    @classmethod
+    def from_config(cls, cfg, **overrides):
+        """From a dict or another scheduler's `config` (e.g. `DDIMScheduler(...).config`)."""
+        cfg = dict(cfg) if isinstance(cfg, dict) else dict(vars(cfg))
+        cfg.update(overrides)
+        return cls(**cfg)
+
+    def _reset(self):
+        self.step_index = None
+        self._x0_prev = None
+        self._taken = 0
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        T = self.config.num_train_timesteps
+        self.num_inference_steps = num_inference_steps
+        ts = np.round(np.arange(T, 0, -T / num_inference_steps)).astype(np.int64) - 1
+        self.timesteps = torch.from_numpy(ts.copy())
+        sig = self.sigma_table[self.timesteps]
+        last = torch.zeros(1) if self.config.final_sigmas_type == "zero" else self.sigma_table[:1]
+        self.sigmas = torch.cat([sig, last]).to(torch.float32)
+        self._reset()
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def solver_order_at(self, i, begin_index=0):
+        """Order of the update at step index i of a run that started at `begin_index` (diffusers' step(): first order
+        at the first step of a run, at solver_order 1, and at the last step under final_sigmas_type "zero",
+        euler_at_final, or lower_order_final below 15 steps).  diffusers' other small-n rule, `lower_order_second` at
+        i = n - 2, caps the order at 2 and so changes nothing for solver_order <= 2."""
+        cfg, n = self.config, self.num_inference_steps
+        if n is None:
+            raise RuntimeError("call set_timesteps() first")
+        if not begin_index <= i < n:
+            raise IndexError(f"step index {i} outside [{begin_index}, {n})")
+        last = i == n - 1 and (cfg.euler_at_final or (cfg.lower_order_final and n < 15)
+                               or cfg.final_sigmas_type == "zero")
+        return 1 if (cfg.solver_order == 1 or i == begin_index or last) else 2
+
+    def multistep_coefficients(self, i, begin_index=0):
+        """(alpha_i, sigma_i, c_x, c_0, c_1) of step index i: x0 = alpha_i x - sigma_i v, x' = c_x x - c_0 x0 + c_1 x0_prev.
+        Float64 arithmetic on the float32 sigma table; a step that ends at sigma = 0 returns x0 exactly (c_x = 0,
+        c_0 = -1, c_1 = 0), so no inf or NaN reaches the kernel."""
+        order = self.solver_order_at(i, begin_index)
+        sg = [float(s) for s in self.sigmas]
+
+        def alpha(s):
+            return 1.0 / math.sqrt(s * s + 1.0)
+        s0, s1 = sg[i], sg[i + 1]
+        a_i, sd_i = alpha(s0), s0 * alpha(s0)
+        if s1 == 0.0:
+            return a_i, sd_i, 0.0, -1.0, 0.0
+        h = math.log(s0) - math.log(s1)                                    # lambda = -log sigma
+        A = alpha(s1) * math.expm1(-h)
+        c_x = (s1 * alpha(s1)) / sd_i
+        B = 0.0
+        if order == 2:
+            r = (math.log(sg[i - 1]) - math.log(s0)) / h
+            B = 0.5 * A / r
+        return a_i, sd_i, c_x, A + B, B
+
+    def step(self, model_output, timestep, sample, return_dict=True, **unused):
+        """One update on tensors (v-prediction `model_output`), keeping the step index and the last x0 like diffusers."""
+        if self.step_index is None:
+            hits = (self.timesteps == int(timestep)).nonzero()
+            if len(hits) == 0:
+                raise ValueError(f"timestep {int(timestep)} is not in this schedule")
+            self.step_index = int(hits[0])
+        i = self.step_index
+        a_i, sd_i, c_x, c_0, c_1 = self.multistep_coefficients(i, begin_index=i - self._taken)
+        x0 = a_i * sample - sd_i * model_output
+        prev = c_x * sample - c_0 * x0
+        if c_1 != 0.0:
+            prev = prev + c_1 * self._x0_prev
+        self._x0_prev = x0
+        self.step_index += 1
+        self._taken += 1
+        out = SimpleNamespace(prev_sample=prev, pred_original_sample=x0)
+        return out if return_dict else (prev,)
