@@ -432,6 +432,15 @@ int vx_overlap_multistep_step(float* latents, int c, int total_frames, int hw, c
                               const int32_t* terms, int max_terms, const int32_t* frame_ids, const float* count,
                               int n_frames, float* x0_history, float alpha_s, float sigma_s, float c_x, float c_0,
                               float c_1, void* stream);
+/* per-frame mean-overlap + ancestral update (DDIM with eta > 0, Euler ancestral in the VP frame; v-prediction): v summed
+ * exactly as in vx_overlap_ddim_step; x0 = alpha_s x - sigma_s v; latents[:, :, frame] = c_x x - c_0 x0 + c_z z, z the
+ * Philox4x32-10 + Box-Muller normal of (seed = seed_hi:seed_lo, step_index, frame, channel, pixel) of csrc/vx_rng.h (the
+ * same on every rank and for any window layout).  hw % 4 == 0; latents / preds 16-byte aligned; c_z == 0 draws nothing.
+ * The host collapses each update to (alpha_s, sigma_s, c_x, c_0, c_z) (scheduler.*.ancestral_coefficients).  */
+int vx_overlap_ancestral_step(float* latents, int c, int total_frames, int hw, const float* preds, int f_window,
+                              const int32_t* terms, int max_terms, const int32_t* frame_ids, const float* count,
+                              int n_frames, float alpha_s, float sigma_s, float c_x, float c_0, float c_z,
+                              uint32_t seed_lo, uint32_t seed_hi, int step_index, void* stream);
 /* NCHW-ish float32 [b, C, f, h, w] -> NHWC bf16 [(b f), h*w, c_pad]  (API-boundary layout change) */
 int vx_ncfhw_to_nhwc(const float* x, int b, int c, int f, int hw, int c_pad, void* out, void* stream);
 /* NHWC float32 [(b f), hw, ld] -> [b, C, f, h*w] float32 */

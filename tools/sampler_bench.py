@@ -2,9 +2,13 @@
 with a chosen sampler and step count (GPU box):
     python tools/sampler_bench.py --scheduler ddim --steps 25
     python tools/sampler_bench.py --scheduler dpm --steps 15 [--order 2]
+    python tools/sampler_bench.py --scheduler euler-a --steps 25
+    python tools/sampler_bench.py --scheduler ddim-eta --eta 1.0 --steps 25
 Prints one JSON line: ms per clip (host clock around whole clips, ending in a device synchronise), the denoise and decode
 milliseconds of the same clips (HIP events), and the average microseconds of the per-step update launch (HIP events
-around each `ops.overlap_ddim_step` / `ops.overlap_multistep_step` of one further, instrumented clip)."""
+around each `ops.overlap_ddim_step` / `ops.overlap_multistep_step` / `ops.overlap_ancestral_step` of one further,
+instrumented clip; for the ancestral samplers also `ddim_update_us`, the DDIM update of the same clip timed the same way,
+for comparison)."""
 import argparse
 import json
 import os
@@ -18,7 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scheduler", choices=("ddim", "dpm"), default="ddim")
+    ap.add_argument("--scheduler", choices=("ddim", "dpm", "ddim-eta", "euler-a"), default="ddim")
+    ap.add_argument("--eta", type=float, default=1.0, help="DDIM eta of --scheduler ddim-eta")
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--order", type=int, choices=(1, 2), default=2, help="DPM-Solver++ solver_order")
     ap.add_argument("--clips", type=int, default=5, help="timed clips")
@@ -46,8 +51,12 @@ def main():
     vae._prepared()
     kw = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", clip_sample=False, steps_offset=1,
               prediction_type="v_prediction", rescale_betas_zero_snr=True, timestep_spacing="trailing")
-    if args.scheduler == "ddim":
-        sched, update = vx.DDIMScheduler(**kw), "overlap_ddim_step"
+    eta = args.eta if args.scheduler == "ddim-eta" else 0.0
+    if args.scheduler in ("ddim", "ddim-eta"):
+        sched = vx.DDIMScheduler(**kw)
+        update = "overlap_ddim_step" if args.scheduler == "ddim" else "overlap_ancestral_step"
+    elif args.scheduler == "euler-a":
+        sched, update = vx.EulerAncestralDiscreteScheduler(**kw), "overlap_ancestral_step"
     else:
         sched, update = vx.DPMSolverMultistepScheduler(**kw, solver_order=args.order), "overlap_multistep_step"
     pipe = vx.VExpressPipeline(vae=vae, reference_net=refnet, denoising_unet=unet, scheduler=sched)
@@ -66,10 +75,10 @@ def main():
     audio = inp["audio_embeddings"].to(elem).contiguous()
 
     def one_clip(ev=None):
-        lat = inp["latents"].clone()
+        lat = inp["latents"] * pipe.scheduler.init_noise_sigma     # (1 but for Euler ancestral)
         if ev:
             ev[0].record()
-        pipe.denoise(lat, kps_tokens, audio, timesteps, windows, 3.5)
+        pipe.denoise(lat, kps_tokens, audio, timesteps, windows, 3.5, eta=eta, noise_seed=12345)
         if ev:
             ev[1].record()
         video = pipe.decode_latents(lat)
@@ -90,26 +99,40 @@ def main():
     decode_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / args.clips
     assert video.shape == (1, 3, F, 512, 512) and torch.isfinite(video).all()
     # one more clip with events around every update launch (kept out of the timed clips above)
-    orig, marks = getattr(ops, update), []
+    def update_launch_us(name):
+        orig, marks = getattr(ops, name), []
 
-    def marked(*a, **k):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        orig(*a, **k)
-        e.record()
-        marks.append((s, e))
-    setattr(ops, update, marked)
-    try:
-        one_clip()
-    finally:
-        setattr(ops, update, orig)
-    torch.cuda.synchronize()
-    update_us = 1e3 * sum(s.elapsed_time(e) for s, e in marks) / len(marks)
+        def marked(*a, **k):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            orig(*a, **k)
+            e.record()
+            marks.append((s, e))
+        setattr(ops, name, marked)
+        try:
+            one_clip()
+        finally:
+            setattr(ops, name, orig)
+        torch.cuda.synchronize()
+        return len(marks), 1e3 * sum(s.elapsed_time(e) for s, e in marks) / len(marks)
+    n_updates, update_us = update_launch_us(update)
+    ddim_us = None
+    if update == "overlap_ancestral_step":
+        # the DDIM update of the same clip, timed the same way (eta = 0 on a DDIM scheduler of the same steps)
+        sched_a, eta_a = pipe.scheduler, eta
+        pipe.scheduler, eta = vx.DDIMScheduler(**kw), 0.0
+        pipe.scheduler.set_timesteps(args.steps)
+        try:
+            ddim_us = round(update_launch_us("overlap_ddim_step")[1], 2)
+        finally:
+            pipe.scheduler, eta = sched_a, eta_a
     print(json.dumps(dict(
-        scheduler=args.scheduler, order=args.order if args.scheduler == "dpm" else None, steps=args.steps,
+        scheduler=args.scheduler, order=args.order if args.scheduler == "dpm" else None,
+        eta=eta if args.scheduler == "ddim-eta" else None, steps=args.steps,
         config="512x512, 16 frames (one window), CFG 3.5, synthetic weights, bf16", clips=args.clips,
         ms_per_clip=round(clip_ms, 2), denoise_ms=round(denoise_ms, 2), decode_ms=round(decode_ms, 2),
-        frames_per_s=round(F * 1e3 / clip_ms, 3), update_launches=len(marks), update_us=round(update_us, 2))))
+        frames_per_s=round(F * 1e3 / clip_ms, 3), update_launches=n_updates, update_us=round(update_us, 2),
+        ddim_update_us=ddim_us)))
 
 
 if __name__ == "__main__":

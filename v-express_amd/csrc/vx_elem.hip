@@ -2,6 +2,7 @@
 // UNet; they exist so that latents, predictions and the DDIM state never leave HBM (the reference round-trips
 // them through the host every window: pipelines/v_express_pipeline.py:521,538,572).
 #include "vx_common.h"
+#include "vx_rng.h"
 #include "../../include/vexpress_hip.h"
 
 namespace {
@@ -188,6 +189,52 @@ __global__ void overlap_multistep_kernel(float* latents, int c, int total_frames
   if (c_1 != 0.f) out += c_1 * x0_history[off];
   x0_history[off] = x0;
   latents[off] = out;
+}
+
+// One ancestral update per frame (DDIM with eta > 0, Euler ancestral in the VP frame; v-prediction): the averaged v
+// exactly as overlap_ddim_kernel sums it, x0 = alpha_s x - sigma_s v, x' = c_x x - c_0 x0 + c_z z, with z the
+// counter-based normals of vx_rng.h for (seed, step, frame, channel, pixel).  One thread per (frame slot, channel, pixel
+// quad): float4 loads and stores (hw % 4 == 0, 16-byte aligned rows) and one Philox call; c_z == 0 skips the generator.
+__global__ void overlap_ancestral_kernel(float* latents, int c, int total_frames, int hw, const float* preds,
+                                         int f_window, const int32_t* terms, int max_terms, const int32_t* frame_ids,
+                                         const float* count, int n_frames, float alpha_s, float sigma_s, float c_x,
+                                         float c_0, float c_z, uint32_t seed_lo, uint32_t seed_hi, int step_index) {
+  const int hq = hw >> 2;
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // (frame slot, channel, pixel quad)
+  long total = (long)n_frames * c * hq;
+  if (idx >= total) return;
+  int q = (int)(idx % hq);
+  int ch = (int)((idx / hq) % c);
+  int fs = (int)(idx / ((long)hq * c));
+  int fr = frame_ids[fs];
+  float ic = count[fs];
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  bool first = true;
+  for (int t = 0; t < max_terms; ++t) {
+    int slot = terms[(fs * max_terms + t) * 2 + 0];
+    int li = terms[(fs * max_terms + t) * 2 + 1];
+    if (slot < 0) continue;
+    const float4 p = *reinterpret_cast<const float4*>(preds + (((size_t)slot * c + ch) * f_window + li) * hw + 4 * q);
+    const float4 term = make_float4(p.x / ic, p.y / ic, p.z / ic, p.w / ic);
+    if (first) {
+      v = term;
+    } else {
+      v.x = v.x + term.x; v.y = v.y + term.y; v.z = v.z + term.z; v.w = v.w + term.w;
+    }
+    first = false;
+  }
+  float4* lp = reinterpret_cast<float4*>(latents + ((size_t)ch * total_frames + fr) * hw + 4 * q);
+  const float4 x = *lp;
+  float4 out;
+  out.x = c_x * x.x - c_0 * (alpha_s * x.x - sigma_s * v.x);
+  out.y = c_x * x.y - c_0 * (alpha_s * x.y - sigma_s * v.y);
+  out.z = c_x * x.z - c_0 * (alpha_s * x.z - sigma_s * v.z);
+  out.w = c_x * x.w - c_0 * (alpha_s * x.w - sigma_s * v.w);
+  if (c_z != 0.f) {                                          // uniform: a kernel argument
+    const float4 z = vx_normal4((uint32_t)q, (uint32_t)ch, (uint32_t)fr, (uint32_t)step_index, seed_lo, seed_hi);
+    out.x += c_z * z.x; out.y += c_z * z.y; out.z += c_z * z.z; out.w += c_z * z.w;
+  }
+  *lp = out;
 }
 
 // x fp32 [b, c, f, hw] -> out bf16 [(b f), hw, c_pad]; LDS transpose so both sides are coalesced for wide c
@@ -401,6 +448,21 @@ extern "C" int vx_overlap_multistep_step(float* latents, int c, int total_frames
                      latents, c, total_frames, hw, preds, f_window, terms, max_terms, frame_ids, count, n_frames,
                      x0_history, alpha_s, sigma_s, c_x, c_0, c_1);
   return vx_check_launch("vx_overlap_multistep_step");
+}
+
+extern "C" int vx_overlap_ancestral_step(float* latents, int c, int total_frames, int hw, const float* preds,
+                                         int f_window, const int32_t* terms, int max_terms, const int32_t* frame_ids,
+                                         const float* count, int n_frames, float alpha_s, float sigma_s, float c_x,
+                                         float c_0, float c_z, uint32_t seed_lo, uint32_t seed_hi, int step_index,
+                                         void* stream) {
+  VX_REQUIRE(latents && preds && terms && frame_ids && count && n_frames > 0 && max_terms > 0 && c > 0 &&
+                 total_frames > 0 && f_window > 0 && hw > 0 && hw % 4 == 0 && step_index >= 0 &&
+                 ((uintptr_t)latents % 16) == 0 && ((uintptr_t)preds % 16) == 0,
+             "vx_overlap_ancestral_step: bad arguments (hw %% 4 == 0 and 16-byte aligned latents / preds required)");
+  hipLaunchKernelGGL(overlap_ancestral_kernel, grid1d((long)n_frames * c * (hw / 4)), dim3(256), 0,
+                     (hipStream_t)stream, latents, c, total_frames, hw, preds, f_window, terms, max_terms, frame_ids,
+                     count, n_frames, alpha_s, sigma_s, c_x, c_0, c_z, seed_lo, seed_hi, step_index);
+  return vx_check_launch("vx_overlap_ancestral_step");
 }
 
 extern "C" int vx_ncfhw_to_nhwc(const float* x, int b, int c, int f, int hw, int c_pad, void* out, void* stream) {

@@ -1355,6 +1355,23 @@ def overlap_multistep_step(latents, preds, terms, frame_ids, counts, x0_history,
                                            *[float(v) for v in coef], _stream()), "vx_overlap_multistep_step")
 
 
+def overlap_ancestral_step(latents, preds, terms, frame_ids, counts, coef, seed, step_index):
+    """Ancestral update of `frame_ids` (DDIM with eta > 0, Euler ancestral): latents fp32 [1,C,F,h,w] updated in place,
+    preds fp32 [slots, C, f, hw]; coef = (alpha, sigma, c_x, c_0, c_z) of the scheduler's ancestral_coefficients; the
+    noise is the kernel's counter-based normal of (seed: 64 bits, step_index, frame, channel, pixel)."""
+    _, c, F, h, w = latents.shape
+    if (h * w) % 4 or not latents.is_contiguous() or not preds.is_contiguous():
+        raise TypeError("overlap_ancestral_step: contiguous latents / preds with h * w % 4 == 0 required")
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64 or int(step_index) < 0:
+        raise ValueError("overlap_ancestral_step: seed must fit 64 unsigned bits and step_index be >= 0")
+    n = frame_ids.numel()
+    L.check(_lib.vx_overlap_ancestral_step(_ptr(latents), c, F, h * w, _ptr(preds), preds.shape[2], _ptr(terms),
+                                           terms.shape[1], _ptr(frame_ids), _ptr(counts), n,
+                                           *[float(v) for v in coef], seed & 0xFFFFFFFF, seed >> 32, int(step_index),
+                                           _stream()), "vx_overlap_ancestral_step")
+
+
 def ncfhw_to_nhwc(x, c_pad=None):
     """fp32 [b, C, f, h, w] -> bf16 [(b f), h*w, c_pad]."""
     b, c, f, h, w = x.shape

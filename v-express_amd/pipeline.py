@@ -29,7 +29,7 @@ from .context import get_context_scheduler, overlap_plan
 from .distributed import (DistContext, MixedUnitSchedule, UnitSchedule, choose_frame_shards, choose_mixed_shards,
                           split_frames)
 from .mutual_self_attention import ReferenceAttentionControl
-from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
 
 
 def _in_unet_element_type(fn):
@@ -194,31 +194,52 @@ class VExpressPipeline:
         return latents.to(device=device, dtype=torch.float32) * self.scheduler.init_noise_sigma
 
     # ------------------------------------------------------------------ the hot loop
-    def _multistep(self):
-        """False: DDIM (vx_overlap_ddim_step); True: DPM-Solver++ (vx_overlap_multistep_step).  Any other scheduler raises
-        TypeError before anything runs: the fused updates are the only ones the loop has."""
+    def _sampler(self, eta=0.0):
+        """The update the loop runs: "ddim" (vx_overlap_ddim_step), "ddim-eta" (DDIM with eta > 0), "dpm" (DPM-Solver++,
+        vx_overlap_multistep_step) or "euler-a" (Euler ancestral); the two ancestral ones run vx_overlap_ancestral_step.
+        Any other scheduler raises TypeError before anything runs: the fused updates are the only ones the loop has.
+        eta is honoured by DDIM only: eta != 0 with another scheduler raises NotImplementedError."""
         if isinstance(self.scheduler, DDIMScheduler):
-            return False
-        if isinstance(self.scheduler, DPMSolverMultistepScheduler):
-            return True
+            if eta < 0:
+                raise ValueError(f"eta must be >= 0, got {eta}")
+            return "ddim" if eta == 0.0 else "ddim-eta"
+        if isinstance(self.scheduler, (DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler)):
+            if eta != 0.0:
+                raise NotImplementedError(f"eta != 0 is a DDIM option; {type(self.scheduler).__name__} does not take it")
+            return "dpm" if isinstance(self.scheduler, DPMSolverMultistepScheduler) else "euler-a"
         raise TypeError(f"the denoising loop drives v_express_amd.DDIMScheduler or "
-                        f"v_express_amd.DPMSolverMultistepScheduler, not {type(self.scheduler).__name__}")
+                        f"v_express_amd.DPMSolverMultistepScheduler or v_express_amd.EulerAncestralDiscreteScheduler, "
+                        f"not {type(self.scheduler).__name__}")
+
+    def _ancestral_coefficients(self, kind, timesteps, begin_index, eta):
+        """Per-step (alpha_s, sigma_s, c_x, c_0, c_z) of an ancestral sampler, resolved on the host before the loop."""
+        if kind == "ddim-eta":
+            return [self.scheduler.ancestral_coefficients(t, eta) for t in timesteps]
+        return [self.scheduler.ancestral_coefficients(begin_index + i) for i in range(len(timesteps))]
 
     @_in_unet_element_type
     def denoise(self, latents, kps_tokens, audio, timesteps, windows, guidance_scale, callback=None,
-                callback_steps=1, *, begin_index=None):
+                callback_steps=1, *, begin_index=None, eta=0.0, noise_seed=None):
         """pipelines/v_express_pipeline.py:526-583.  latents fp32 [1,4,F,h,w] (device, updated in place);
         kps_tokens bf16 [b, F, hw, C0]; audio bf16 [b, F, n_ctx, 768] with b = 2 (uncond, cond) under classifier-free
         guidance (guidance_scale > 1, :443) and b = 1 (the conditional row only) without.
-        DPM-Solver++: `timesteps` are the scheduler's from step index `begin_index` on (default: its last
-        len(timesteps)); each frame gets exactly one update per timestep, so the multistep history is per frame."""
-        multistep = self._multistep()
-        if multistep:
-            all_ts = self.scheduler.timesteps.tolist()
+        DPM-Solver++ and the ancestral samplers: `timesteps` are the scheduler's from step index `begin_index` on
+        (default: its last len(timesteps)); each frame gets exactly one update per timestep, so the multistep history is
+        per frame.  Ancestral samplers (DDIM with eta > 0, Euler ancestral) draw the noise of step index i on the device
+        from `noise_seed` (64 bits, required), keyed by (step index, frame, channel, pixel) only.  Euler ancestral: the
+        latents come and go in the scheduler's (VE) frame; the loop runs in the VP frame x / sqrt(1 + sigma^2)."""
+        kind = self._sampler(eta)
+        if kind != "ddim":
+            all_ts = [int(t) for t in self.scheduler.timesteps.tolist()]
             if begin_index is None:
                 begin_index = len(all_ts) - len(timesteps)
             if [int(t) for t in timesteps] != all_ts[begin_index:begin_index + len(timesteps)]:
-                raise ValueError("DPM-Solver++: timesteps must be the scheduler's own, from step index begin_index on")
+                raise ValueError(f"{type(self.scheduler).__name__}: timesteps must be the scheduler's own, from step "
+                                 f"index begin_index on")
+        ancestral = kind in ("ddim-eta", "euler-a")
+        if ancestral and noise_seed is None:
+            raise ValueError(f"the {kind} sampler draws noise on the device: pass noise_seed")
+        multistep = kind == "dpm"
         unet, dc, dev = self.denoising_unet, self.dist, latents.device
         _, C, F, H, W = latents.shape
         hw = H * W
@@ -328,6 +349,12 @@ class VExpressPipeline:
         x0_hist = torch.empty_like(latents) if multistep else None
         coefs = [self.scheduler.multistep_coefficients(begin_index + i, begin_index)
                  for i in range(len(timesteps))] if multistep else None
+        if ancestral:
+            coefs = self._ancestral_coefficients(kind, timesteps, begin_index, eta)
+            noise_seed = int(noise_seed)
+        euler_a = kind == "euler-a"
+        if euler_a and timesteps:
+            latents.mul_(1.0 / self.scheduler.frame_scale(begin_index))          # VE -> VP, once
         for i, t in enumerate(timesteps):
             t = int(t)
             for rows, gathers, kps, ehs, akv, f_loc, shard, s0, n_slots in calls:
@@ -343,10 +370,18 @@ class VExpressPipeline:
             ops.combine_units(gathered, uidx, C, f, hw, guidance_scale if do_cfg else 1.0, preds)
             if multistep:
                 ops.overlap_multistep_step(latents, preds, terms, frame_ids, counts, x0_hist, coefs[i])
+            elif ancestral:
+                ops.overlap_ancestral_step(latents, preds, terms, frame_ids, counts, coefs[i], noise_seed,
+                                           begin_index + i)
             else:
                 ops.overlap_ddim_step(latents, preds, terms, frame_ids, counts, self.scheduler.step_coefficients(t))
             if callback is not None and i % callback_steps == 0:
-                callback(i, t, latents)
+                # Euler ancestral: the callback sees the scheduler's own (VE) frame, as the reference's does
+                callback(i, t, latents * self.scheduler.frame_scale(begin_index + i + 1) if euler_a else latents)
+        if euler_a and timesteps:
+            scale = self.scheduler.frame_scale(begin_index + len(timesteps))
+            if scale != 1.0:                                                     # a run that stops before sigma = 0
+                latents.mul_(scale)
         return latents
 
     @torch.no_grad()
@@ -380,10 +415,9 @@ class VExpressPipeline:
                  context_overlap=4, reference_attention_weight=1., audio_attention_weight=1.,
                  num_pad_audio_frames=2, do_multi_devices_inference=False, save_gpu_memory=False,
                  reference_latents=None, kps_features=None, audio_embeddings=None, latents=None,
-                 output_device="cpu", decode=True, **kwargs):
-        if eta != 0.0:
-            raise NotImplementedError("eta != 0 is unused by V-Express")
-        self._multistep()                      # an unsupported scheduler fails here, before the prologue
+                 noise_seed: Optional[int] = None, output_device="cpu", decode=True, **kwargs):
+        # an unsupported scheduler, or eta with one other than DDIM, fails here, before the prologue
+        kind = self._sampler(eta)
         dev = self.device
         do_cfg = guidance_scale > 1.0
         # timesteps (retrieve_timesteps + get_timesteps, :448-449)
@@ -391,6 +425,8 @@ class VExpressPipeline:
         init_t = min(int(num_inference_steps * strength), num_inference_steps)
         begin_index = max(num_inference_steps - init_t, 0)
         timesteps = self.scheduler.timesteps[begin_index:].tolist()
+        if kind in ("ddim-eta", "euler-a"):
+            self._ancestral_coefficients(kind, timesteps, begin_index, eta)     # e.g. eta too large: ValueError here
         writer = ReferenceAttentionControl(self.reference_net, do_classifier_free_guidance=do_cfg, mode="write",
                                            batch_size=1, fusion_blocks="full")
         reader = ReferenceAttentionControl(self.denoising_unet, do_classifier_free_guidance=do_cfg, mode="read",
@@ -421,6 +457,14 @@ class VExpressPipeline:
             # every rank drew from its own CPU generator; the loop needs identical step-start latents on all ranks
             # (each rank's UNet inputs are gathered from them and every rank applies the DDIM update): rank 0's draw wins
             lat = self.dist.broadcast(lat.contiguous(), src=0)
+        if kind in ("ddim-eta", "euler-a") and noise_seed is None:
+            # the ancestral noise is drawn on the device from one 64-bit seed, taken from the generator AFTER the
+            # initial latents (which so stay what they are for a given generator); rank 0's seed wins, like its latents
+            g = generator[0] if isinstance(generator, list) else generator
+            seed = torch.randint(0, 2 ** 63 - 1, (1,), generator=g)
+            if self.dist.enabled:
+                seed = self.dist.broadcast(seed.to(lat.device), src=0).cpu()
+            noise_seed = int(seed)
         if kps_tokens is None:
             b2, c0, F, h, w = kps_features.shape
             kps_tokens = ops.ncfhw_to_nhwc(kps_features.to(dev), c0).view(b2, F, h * w, c0)
@@ -430,7 +474,7 @@ class VExpressPipeline:
         if timed:
             ev[0].record()
         self.denoise(lat, kps_tokens, audio, timesteps, windows, guidance_scale, callback, callback_steps or 1,
-                     begin_index=begin_index)
+                     begin_index=begin_index, eta=eta, noise_seed=noise_seed)
         if timed:
             ev[1].record()
         reader.clear()

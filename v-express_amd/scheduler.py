@@ -6,7 +6,9 @@ restated from its published behaviour — SURVEY.md Appendix A).
 Host side only: the per-step update itself runs in the fused `vx_overlap_ddim_step` kernel, fed by
 `step_coefficients(t)`; `step()` is kept as the reference-compatible tensor API.  DPMSolverMultistepScheduler (the
 second-order multistep sampler of the reference's scheduler list, pipelines/v_express_pipeline.py:83-90) feeds
-`vx_overlap_multistep_step` the same way through `multistep_coefficients(i)`.
+`vx_overlap_multistep_step` the same way through `multistep_coefficients(i)`.  The ancestral samplers (DDIM with
+eta > 0 through `DDIMScheduler.ancestral_coefficients(t, eta)`, EulerAncestralDiscreteScheduler through
+`ancestral_coefficients(i)`) feed `vx_overlap_ancestral_step`, which draws its noise on the device.
 """
 from types import SimpleNamespace
 
@@ -85,6 +87,23 @@ class DDIMScheduler:
         four scalars of DDIMScheduler.step for v-prediction, eta=0."""
         a, a_prev = self._alphas(t)
         return (float(a ** 0.5), float((1 - a) ** 0.5), float(a_prev ** 0.5), float((1 - a_prev) ** 0.5))
+
+    def ancestral_coefficients(self, t, eta):
+        """(alpha_s, sigma_s, c_x, c_0, c_z) of DDIM with `eta` at timestep t: x0 = alpha_s x - sigma_s v,
+        x' = c_x x - c_0 x0 + c_z z - diffusers' sqrt(a') x0 + k eps + sigma_eta z with eps written through x and x0
+        (k = sqrt(1 - a' - sigma_eta^2)).  Float64 arithmetic on the float32 table; the last step (a' = 1) returns x0
+        exactly.  ValueError for eta < 0 or when 1 - a' - sigma_eta^2 < 0 (diffusers would compute NaN; eta > 1 can)."""
+        eta = float(eta)
+        if not eta >= 0.0:
+            raise ValueError(f"eta must be >= 0, got {eta}")
+        a, ap = (float(v) for v in self._alphas(t))
+        var = (1.0 - ap) / (1.0 - a) * (1.0 - a / ap)
+        kk = 1.0 - ap - eta * eta * var                # eta = 1 at a = 0: exactly 0
+        if kk < -1e-12:
+            raise ValueError(f"eta={eta}: 1 - alpha_prev - sigma_eta^2 = {kk:.3g} < 0 at timestep {int(t)}")
+        sig, k = eta * math.sqrt(var), math.sqrt(max(kk, 0.0))
+        sa, s1a = math.sqrt(a), math.sqrt(1.0 - a)
+        return sa, s1a, k / s1a, -(math.sqrt(ap) - k * sa / s1a), sig
 
     def step(self, model_output, timestep, sample, eta=0.0, **unused):
         if eta != 0.0:
@@ -226,5 +245,141 @@ class DPMSolverMultistepScheduler:
         self._x0_prev = x0
         self.step_index += 1
         self._taken += 1
+        out = SimpleNamespace(prev_sample=prev, pred_original_sample=x0)
+        return out if return_dict else (prev,)
+
+
+class EulerAncestralDiscreteScheduler:
+    """Euler ancestral sampling for the zero-terminal-SNR v-prediction schedule: the arithmetic of diffusers==0.29.2
+    `EulerAncestralDiscreteScheduler` restated for the options listed in `__init__` (any other value raises
+    NotImplementedError naming the option).
+
+    diffusers works in the VE frame (x_ve = x0 + sigma eps, `scale_model_input` divides by sqrt(1 + sigma^2)).  The loop
+    runs in the VP frame x_vp = x_ve / sqrt(1 + sigma^2) - exactly the UNet input - with the update of the fused
+    `vx_overlap_ancestral_step` kernel, fed by `ancestral_coefficients(i)`:
+        x0 = alpha_s x - sigma_s v ;   x' = c_x x - c_0 x0 + c_z z
+    `step()` is the stateful diffusers-style tensor API in the VE frame.
+    """
+    order = 1
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 trained_betas=None, prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0,
+                 rescale_betas_zero_snr=False, **unused):
+        # (clip_sample, set_alpha_to_one, ... of a DDIM configuration are not parameters of this sampler: ignored, as
+        # diffusers' from_config does)
+        for name, value, ok in (("trained_betas", trained_betas, trained_betas is None),
+                                ("beta_schedule", beta_schedule, beta_schedule == "scaled_linear"),
+                                ("prediction_type", prediction_type, prediction_type == "v_prediction"),
+                                ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing")):
+            if not ok:
+                raise NotImplementedError(f"EulerAncestralDiscreteScheduler: {name}={value!r} is not built")
+        self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
+        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, 0)
+        if rescale_betas_zero_snr:
+            # the zero-SNR table ends at alphas_cumprod = 0: diffusers clamps it so that the first sigma is finite
+            self.alphas_cumprod[-1] = 2 ** -24
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, prediction_type=prediction_type,
+                                      timestep_spacing=timestep_spacing, steps_offset=steps_offset,
+                                      rescale_betas_zero_snr=rescale_betas_zero_snr)
+        # sigma(t) = sqrt((1 - abar_t) / abar_t) in float32, as diffusers computes it
+        self.sigma_table = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
+        self.sigmas = torch.cat([self.sigma_table.flip(0), torch.zeros(1)]).to(torch.float32)
+        self.timesteps = torch.linspace(0, num_train_timesteps - 1, num_train_timesteps,
+                                        dtype=torch.float64).flip(0).to(torch.float32)
+        self.num_inference_steps = None
+        self._step_index = None
+        self._begin_index = None
+
+    @classmethod
+    def from_config(cls, cfg, **overrides):
+        """From a dict or another scheduler's `config` (e.g. `DDIMScheduler(...).config`)."""
+        cfg = dict(cfg) if isinstance(cfg, dict) else dict(vars(cfg))
+        cfg.update(overrides)
+        return cls(**cfg)
+
+    @property
+    def init_noise_sigma(self):
+        """diffusers: the largest sigma under "linspace" / "trailing" spacing (a float32 tensor)."""
+        return self.sigmas.max()
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    @property
+    def begin_index(self):
+        return self._begin_index
+
+    def set_begin_index(self, begin_index=0):
+        self._begin_index = begin_index
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        T = self.config.num_train_timesteps
+        self.num_inference_steps = num_inference_steps
+        ts = np.arange(T, 0, -T / num_inference_steps).round().astype(np.float32) - 1
+        self.timesteps = torch.from_numpy(ts.copy())
+        sig = self.sigma_table[self.timesteps.long()]
+        self.sigmas = torch.cat([sig, torch.zeros(1)]).to(torch.float32)
+        self._step_index = None
+        self._begin_index = None
+
+    def _init_step_index(self, timestep):
+        if self._begin_index is not None:
+            self._step_index = self._begin_index
+            return
+        hits = (self.timesteps == float(timestep)).nonzero()
+        if len(hits) == 0:
+            raise ValueError(f"timestep {float(timestep)} is not in this schedule")
+        self._step_index = int(hits[1 if len(hits) > 1 else 0])
+
+    def scale_model_input(self, sample, timestep=None):
+        """x_ve -> x_vp = x_ve / sqrt(1 + sigma^2) at the current step (diffusers' scaling of the UNet input)."""
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        sigma = self.sigmas[self._step_index]
+        return sample / ((sigma ** 2 + 1) ** 0.5)
+
+    def ancestral_coefficients(self, i):
+        """(alpha_s, sigma_s, c_x, c_0, c_z) of step index i in the VP frame: x0 = alpha_s x - sigma_s v,
+        x' = c_x x - c_0 x0 + c_z z with x, x' = x_ve / sqrt(1 + sigma^2) at sigmas[i], sigmas[i + 1].  Float64
+        arithmetic on the float32 sigmas; a step that ends at sigma = 0 returns x0 exactly (c_x = 0, c_0 = -1, c_z = 0)."""
+        n = self.num_inference_steps
+        if n is None:
+            raise RuntimeError("call set_timesteps() first")
+        if not 0 <= i < n:
+            raise IndexError(f"step index {i} outside [0, {n})")
+        s, s1 = float(self.sigmas[i]), float(self.sigmas[i + 1])
+        r = math.sqrt(1.0 + s * s)
+        alpha_s, sigma_s = 1.0 / r, s / r
+        if s1 == 0.0:
+            return alpha_s, sigma_s, 0.0, -1.0, 0.0
+        s_up = math.sqrt(s1 * s1 * (s * s - s1 * s1) / (s * s))
+        s_down = math.sqrt(s1 * s1 - s_up * s_up)
+        r1 = math.sqrt(1.0 + s1 * s1)
+        return alpha_s, sigma_s, r * s_down / (s * r1), -(1.0 - s_down / s) / r1, s_up / r1
+
+    def frame_scale(self, i):
+        """sqrt(1 + sigmas[i]^2): x_ve = frame_scale(i) x_vp at step index i (1 at the final sigma = 0)."""
+        s = float(self.sigmas[i])
+        return math.sqrt(1.0 + s * s)
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, **unused):
+        """One update on tensors in the VE frame (v-prediction `model_output`, diffusers' arithmetic in float32), noise
+        drawn with torch.randn on `generator`, keeping the step index like diffusers."""
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        i = self._step_index
+        sigma = self.sigmas[i]
+        sample = sample.to(torch.float32)
+        x0 = model_output * (-sigma / (sigma ** 2 + 1) ** 0.5) + (sample / (sigma ** 2 + 1))
+        sigma_from, sigma_to = self.sigmas[i], self.sigmas[i + 1]
+        sigma_up = (sigma_to ** 2 * (sigma_from ** 2 - sigma_to ** 2) / sigma_from ** 2) ** 0.5
+        sigma_down = (sigma_to ** 2 - sigma_up ** 2) ** 0.5
+        prev = sample + (sample - x0) / sigma * (sigma_down - sigma)
+        gen_dev = generator.device if generator is not None else model_output.device
+        noise = torch.randn(model_output.shape, generator=generator, dtype=model_output.dtype, device=gen_dev)
+        prev = (prev + noise.to(model_output.device) * sigma_up).to(model_output.dtype)
+        self._step_index += 1
         out = SimpleNamespace(prev_sample=prev, pred_original_sample=x0)
         return out if return_dict else (prev,)
