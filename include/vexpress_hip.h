@@ -418,6 +418,19 @@ int vx_cfg_combine(const float* unet_out, int ld, int c, int f, int hw, float gu
 int vx_pack_rows(const float* src, int ld, int64_t rows, int c, float* dst, void* stream);
 int vx_combine_units(const float* gathered, const int32_t* unit_index, int n_windows, int halves, int shards, int c,
                      int f, int hw, float guidance, float* preds, void* stream);
+/* CFG combine with the rescale of Lin et al. 2024 (diffusers rescale_noise_cfg, `guidance_rescale` = phi): gathered /
+ * unit_index as vx_combine_units takes them, with both CFG halves (unit_index int32 [n_windows][2][shards]); per window
+ * g = u + s (c - u) and preds[w] = g * (1 + phi (std(c) / std(g) - 1)), std the unbiased standard deviation over the
+ * window's c * f * hw values (a reflected window counts its duplicated frames twice).  Two launches: (count, mean, M2)
+ * partials per (window, frame of the window, chunk of 1024 pixels), each from two passes over its values, written to
+ * workspace (float32, vx_guidance_rescale_ws_floats(n_windows, f, hw) elements, caller-owned); then a merge of a
+ * window's partials in ascending (frame, chunk) order (pairwise formula, double precision) and the scaled combine.
+ * No atomics: the result does not depend on the number of shards, on the unit a frame travelled in, or on the number
+ * of windows in the launch.  phi == 0 skips the statistics and writes exactly what vx_combine_units writes. */
+int64_t vx_guidance_rescale_ws_floats(int n_windows, int f, int hw);
+int vx_guidance_rescale(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c, int f,
+                        int hw, float guidance, float phi, float* workspace, int64_t ws_floats, float* preds,
+                        void* stream);
 /* per-frame mean-overlap + DDIM v-prediction step (eta=0):  v = sum_t (pred[term_slot[t]] / count) ;
  * latents[:, :, frame] = step(v).  terms: int32 [n_frames][max_terms][2] = (window slot, latent idx) or -1.
  * pipelines/v_express_pipeline.py:552-572 + diffusers DDIMScheduler.step.  */

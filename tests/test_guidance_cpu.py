@@ -1,0 +1,297 @@
+"""Guidance controls on the host: the CFG rescale (`guidance_rescale`) and the guidance interval (`guidance_start`,
+`guidance_end`) of VExpressPipeline under emulated kernels (tests/fake_ops.py + guidance_restated.guidance_rescale)
+against float64 restatements, the step rule against a table, the unguided steps against the no-CFG route bit for bit,
+every sampler with both features on, the argument errors, and two gloo ranks against one process."""
+import os
+import socket
+
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+import ancestral_restated as A
+import cases
+import dpm_restated as D
+import guidance_restated as G
+
+SEED = (0x9E3779B9 << 32) | 0x7F4A7C15
+PHI = 0.7
+
+
+def rel_l2(a, b):
+    a, b = a.double(), b.double()
+    return ((a - b).norm() / (b.norm() + 1e-300)).item()
+
+
+@pytest.fixture()
+def emulated(monkeypatch):
+    import fake_ops
+    from v_express_amd import ops, prologue, unet_3d, vae
+    fake_ops.install(monkeypatch, ops)
+    monkeypatch.setattr(ops, "overlap_ancestral_step", A.overlap_ancestral_step)
+    monkeypatch.setattr(ops, "overlap_multistep_step", D.overlap_multistep_step)
+    monkeypatch.setattr(ops, "guidance_rescale", G.guidance_rescale)
+    monkeypatch.setattr(unet_3d._UNetBase, "_need_gpu", lambda self: None)
+    monkeypatch.setattr(vae.AutoencoderKLDecoder, "_need_gpu", lambda self: None)
+    monkeypatch.setattr(prologue._Module, "_need_gpu", lambda self: None)
+    monkeypatch.setattr(ops, "_PADDED", {})
+    return ops
+
+
+@pytest.fixture(scope="module")
+def small_pipe():
+    import dist_gpu_worker as W
+    return W.build_pipeline("cpu")
+
+
+def scheduler(kind):
+    from v_express_amd import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
+    return {"ddim": DDIMScheduler, "ddim-eta": DDIMScheduler, "dpm": DPMSolverMultistepScheduler,
+            "euler-a": EulerAncestralDiscreteScheduler}[kind](**G.KWARGS)
+
+
+def _call(pipe, sched, inp, F_, steps, cf, co, guidance=cases.GUIDANCE, **kw):
+    pipe.scheduler = sched
+    kw.setdefault("latents", inp["latents"])
+    return pipe(None, None, None, 64, 64, F_, steps, guidance, context_frames=cf, context_overlap=co,
+                reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD,
+                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
+                audio_embeddings=inp["audio_embeddings"], decode=False, **kw)
+
+
+def _inputs(F_):
+    from v_express_amd import synth
+    return synth.synthetic_inputs(cases.unet_cfg(cases.SMALL), F_, 8, 8)
+
+
+def _oracle_unet(inp):
+    from oracle import unet as OU
+    from v_express_amd import synth
+    cfg, ocfg = cases.unet_cfg(cases.SMALL), cases.oracle_cfg(cases.SMALL)
+    sd3, sd2 = synth.unet3d_state_dict(cfg), synth.refnet_state_dict(cfg)
+    banks = OU.reader_banks(OU.refnet_banks(sd2, ocfg, inp["ref_latents"]))
+    return lambda x, t, e, k: OU.unet3d_forward(sd3, ocfg, x, t, e, k, banks, cases.W_REF, cases.W_AUD)
+
+
+# ------------------------------------------------------------------------------------------------ (1) the rescale
+def test_guidance_rescale_changes_the_clip_and_matches_the_restatement(emulated, small_pipe):
+    """Two windows (F = 6, windows of 4 with overlap 2), 3 DDIM steps, phi = 0.7: the
+    latents differ from phi = 0; every window prediction the op wrote equals the float64 rescale of the UNet outputs it
+    was given to 4 x the error of the float32 torch.std evaluation of the same formula (the kernel test's bound); and
+    the clip matches the restated loop over the oracle UNet.  Fails on a pipeline that ignores guidance_rescale."""
+    from oracle import loop as OL
+    F_, cf, co, steps = 6, 4, 2, 3
+    inp = _inputs(F_)
+    windows = OL.uniform_windows(F_, cf, co)
+    assert len(windows) == 2
+    seen = []
+    orig = emulated.guidance_rescale
+
+    def spy(gathered, uidx, c, f, hw, guidance, phi, ws, preds):
+        orig(gathered, uidx, c, f, hw, guidance, phi, ws, preds)
+        u, cond = G.units(gathered, uidx, c, f, hw)
+        seen.append((u.clone(), cond.clone(), guidance, phi, preds.clone()))
+    emulated.guidance_rescale = spy
+    plain = _call(small_pipe, scheduler("ddim"), inp, F_, steps, cf, co)
+    assert not seen
+    got = _call(small_pipe, scheduler("ddim"), inp, F_, steps, cf, co, guidance_rescale=PHI)
+    assert len(seen) == steps and small_pipe.last_guidance == dict(guided_steps=steps, steps=steps, rescale=PHI,
+                                                                   unguided_schedule=None)
+    assert torch.isfinite(got).all() and rel_l2(got, plain) > 1e-3
+    for u, cond, guidance, phi, preds in seen:
+        assert (guidance, phi) == (cases.GUIDANCE, PHI) and preds.shape == (2, 4, cf, 64)
+        ref = G.combine_rescaled(u, cond, guidance, phi)
+        err = (preds.double() - ref).abs().max().item()
+        base = G.float32_baseline_error(u, cond, guidance, phi)
+        print(f"[guidance_rescale stand-in] max |err| {err:.3g}, float32 torch.std baseline {base:.3g}")
+        assert err <= 4 * base
+    with torch.no_grad():
+        ref = G.restated_loop(_oracle_unet(inp), inp["latents"], windows, cases.GUIDANCE, inp["kps_features"],
+                              inp["audio_embeddings"], steps, "ddim", phi=PHI)
+    r = rel_l2(got, ref)
+    print(f"[__call__ guidance_rescale={PHI}, emulated kernels, {steps} steps] relL2 vs restated loop {r:.4g}, "
+          f"vs phi = 0 {rel_l2(plain, ref):.4g}")
+    assert r <= 5e-2 and r < rel_l2(plain, ref)
+
+
+# ------------------------------------------------------------------------------------------------ (2) defaults
+def test_defaults_build_one_plan_and_never_call_the_new_op(emulated, small_pipe, monkeypatch):
+    F_, cf, co, steps = 6, 4, 2, 2
+    inp = _inputs(F_)
+
+    def boom(*a, **k):
+        raise AssertionError("guidance_rescale ran")
+    monkeypatch.setattr(emulated, "guidance_rescale", boom)
+    plans = []
+    orig = type(small_pipe)._unit_plan
+
+    def counting(self, *a, **k):
+        plans.append(a[-1])
+        return orig(self, *a, **k)
+    monkeypatch.setattr(type(small_pipe), "_unit_plan", counting)
+    base = _call(small_pipe, scheduler("ddim"), inp, F_, steps, cf, co)
+    assert plans == [[0, 1]]
+    assert small_pipe.last_guidance == dict(guided_steps=steps, steps=steps, rescale=0.0, unguided_schedule=None)
+    assert small_pipe.last_schedule == dict(kind="whole units", frame_shards=1, mixed_shards=1, units=4, world=1)
+    same = _call(small_pipe, scheduler("ddim"), inp, F_, steps, cf, co, guidance_rescale=0.0, guidance_start=0,
+                 guidance_end=1)
+    assert plans == [[0, 1]] * 2 and torch.equal(base, same)
+    # without classifier-free guidance the controls change nothing and launch nothing
+    nocfg = cases.cond_only(inp)
+    a = _call(small_pipe, scheduler("ddim"), nocfg, F_, steps, cf, co, guidance=1.0)
+    b = _call(small_pipe, scheduler("ddim"), nocfg, F_, steps, cf, co, guidance=1.0, guidance_rescale=PHI,
+              guidance_end=0.5)
+    assert plans[2:] == [[0], [0]] and torch.equal(a, b) and small_pipe.last_guidance["guided_steps"] == 0
+
+
+# ------------------------------------------------------------------------------------------------ (3), (4) the interval
+def test_guidance_end_zero_is_the_no_cfg_route_bit_for_bit(emulated, small_pipe):
+    F_, cf, co, steps = 6, 4, 2, 3
+    inp = _inputs(F_)
+    off = _call(small_pipe, scheduler("ddim"), inp, F_, steps, cf, co, guidance_end=0.0, guidance_rescale=PHI)
+    lg = small_pipe.last_guidance
+    assert lg["guided_steps"] == 0 and lg["unguided_schedule"] == dict(kind="whole units", frame_shards=1,
+                                                                       mixed_shards=1, units=2, world=1)
+    assert small_pipe.last_schedule["units"] == 4
+    nocfg = _call(small_pipe, scheduler("ddim"), cases.cond_only(inp), F_, steps, cf, co, guidance=1.0)
+    assert torch.equal(off, nocfg)
+    assert not torch.equal(off, _call(small_pipe, scheduler("ddim"), inp, F_, steps, cf, co))
+
+
+def test_interval_equals_a_cfg_run_continued_without_guidance(emulated, small_pipe, monkeypatch):
+    """guidance_end = 0.6, 5 DDIM steps: 3 guided + 2 unguided = the full-CFG run's latents after step index 2, continued
+    by a guidance_scale = 1 call from begin index 3; steps 3-4 run UNet calls of half the batch rows."""
+    F_, cf, co, steps = 6, 4, 2, 5
+    inp = _inputs(F_)
+    unet = small_pipe.denoising_unet
+    rows = []
+    orig = unet.forward_tokens
+
+    def spy(x_in, t, *a, **k):
+        rows.append((int(t), k["b"]))
+        return orig(x_in, t, *a, **k)
+    monkeypatch.setattr(unet, "forward_tokens", spy)
+    small_pipe.units_per_call = 2
+    got = _call(small_pipe, scheduler("ddim"), inp, F_, steps, cf, co, guidance_end=0.6)
+    assert small_pipe.last_guidance["guided_steps"] == 3
+    ts = D.timesteps(steps)
+    per_step = [[b for t, b in rows if t == ts_i] for ts_i in ts]
+    assert per_step[:3] == [[2, 2]] * 3 and per_step[3:] == [[1, 1]] * 2
+    kept = {}
+    _call(small_pipe, scheduler("ddim"), inp, F_, steps, cf, co, callback=lambda i, t, x: kept.setdefault(i, x.clone()))
+    cont = _call(small_pipe, scheduler("ddim"), cases.cond_only(inp), F_, steps, cf, co, guidance=1.0, strength=0.4,
+                 latents=kept[2])
+    assert torch.equal(got, cont)
+
+
+# ------------------------------------------------------------------------------------------------ (5) the step rule
+RULE = [  # (N, start, end, guided step indices)
+    (1, 0.0, 1.0, [0]), (1, 0.0, 0.99, []), (1, 0.5, 1.0, []),
+    (2, 0.0, 0.5, [0]), (2, 0.5, 1.0, [1]), (2, 0.25, 0.75, []),
+    (7, 0.0, 1.0, list(range(7))), (7, 0.0, 0.0, []), (7, 0.3, 0.8, [3, 4]), (7, 1.0, 1.0, []),
+    (25, 0.0, 0.6, list(range(15))), (25, 0.2, 0.8, list(range(5, 20))), (25, 0.0, 0.59, list(range(14))),
+    (50, 0.0, 0.6, list(range(30))), (50, 0.1, 0.9, list(range(5, 45))), (50, 0.5, 0.5, []),
+]
+
+
+@pytest.mark.parametrize("n,start,end,want", RULE)
+def test_step_rule_table(n, start, end, want):
+    from v_express_amd.pipeline import check_guidance, guided_steps
+    mine = G.guided_steps(n, start, end)
+    assert [i for i, g in enumerate(mine) if g] == want
+    assert guided_steps(n, start, end) == mine and check_guidance(0.0, start, end, n)[1] == mine
+    if (n, start, end) == (25, 0.0, 0.6):
+        assert sum(mine) == 15                                 # (14 + 1) / 25 <= 0.6 holds in floats
+
+
+# ------------------------------------------------------------------------------------------------ (6) every sampler
+@pytest.mark.parametrize("kind", ["ddim", "ddim-eta", "dpm", "euler-a"])
+def test_every_sampler_with_both_features_vs_restated_loop(emulated, small_pipe, kind):
+    """Reflected last window [8, 9, 10, 9] (its duplicated frame counts twice in the window's std), 5 steps, phi = 0.7,
+    guidance_end = 0.6: against the restated loop over the oracle UNet.  The unguided steps leave the DPM-Solver++ x0
+    history and Euler ancestral's VP-frame scaling as they are: the restated loop keeps both per step, not per kind."""
+    from oracle import loop as OL
+    F_, cf, co, _ = cases.PIPELINE_CASES["reflected_F11_c4o2"]
+    steps = 5
+    inp = _inputs(F_)
+    eta = 0.5 if kind == "ddim-eta" else 0.0
+    kw = dict(noise_seed=SEED) if kind in ("ddim-eta", "euler-a") else {}
+    got = _call(small_pipe, scheduler(kind), inp, F_, steps, cf, co, eta=eta, guidance_rescale=PHI, guidance_end=0.6,
+                **kw)
+    assert small_pipe.last_guidance["guided_steps"] == 3 and small_pipe.last_guidance["steps"] == 5
+    with torch.no_grad():
+        ref = G.restated_loop(_oracle_unet(inp), inp["latents"], OL.uniform_windows(F_, cf, co), cases.GUIDANCE,
+                              inp["kps_features"], inp["audio_embeddings"], steps, kind, phi=PHI, end=0.6, seed=SEED,
+                              eta=eta)
+    r = rel_l2(got, ref)
+    print(f"[__call__ {kind}, rescale {PHI}, guidance_end 0.6, reflected_F11_c4o2, {steps} steps] relL2 vs restated "
+          f"loop {r:.4g}")
+    assert torch.isfinite(got).all() and r <= 5e-2
+
+
+# ------------------------------------------------------------------------------------------------ (8) errors
+def test_bad_guidance_arguments_fail_before_any_kernel(emulated, small_pipe, monkeypatch):
+    def no_kernels(*a, **k):
+        raise AssertionError("a kernel ran")
+    for name in ("gather_latents", "combine_units", "guidance_rescale", "overlap_ddim_step", "ncfhw_to_nhwc",
+                 "groupnorm", "gemm"):
+        monkeypatch.setattr(emulated, name, no_kernels)
+    inp = _inputs(4)
+    for bad in (dict(guidance_rescale=-0.1), dict(guidance_rescale=1.5), dict(guidance_start=0.7, guidance_end=0.3),
+                dict(guidance_end=1.2), dict(guidance_start=-0.5)):
+        with pytest.raises(ValueError, match="guidance"):
+            _call(small_pipe, scheduler("ddim"), inp, 4, 2, 4, 2, **bad)
+        with pytest.raises(ValueError, match="guidance"):
+            small_pipe.denoise(inp["latents"].clone(), None, None, [999, 499], [[0, 1, 2, 3]], cases.GUIDANCE, **bad)
+
+
+def test_ops_wrapper_checks_its_arguments():
+    from v_express_amd import ops
+    gathered = torch.zeros(2, 4 * 16, 4)
+    uidx = torch.tensor([[[0], [1]]], dtype=torch.int32)
+    ws, preds = torch.zeros(ops.guidance_rescale_ws_floats(1, 4, 16)), torch.zeros(1, 4, 4, 16)
+    assert ws.numel() == 1 * 4 * 1 * 6 and ops.guidance_rescale_ws_floats(2, 16, 4096) == 2 * 16 * 4 * 6
+    with pytest.raises(ValueError, match="both CFG halves"):
+        ops.guidance_rescale(gathered, uidx[:, :1].contiguous(), 4, 4, 16, 3.5, 0.7, ws, preds)
+    with pytest.raises(ValueError, match="phi"):
+        ops.guidance_rescale(gathered, uidx, 4, 4, 16, 3.5, 1.5, ws, preds)
+    with pytest.raises(ValueError, match="workspace"):
+        ops.guidance_rescale(gathered, uidx, 4, 4, 16, 3.5, 0.7, ws[:5], preds)
+    with pytest.raises(ValueError, match="sizes"):
+        ops.guidance_rescale(gathered, uidx, 4, 4, 16, 3.5, 0.7, ws, preds[:, :3].contiguous())
+    with pytest.raises(TypeError):
+        ops.guidance_rescale(gathered, uidx.long(), 4, 4, 16, 3.5, 0.7, ws, preds)
+
+
+# ------------------------------------------------------------------------------------------------ (7) two ranks
+def _worker(rank, world, port, q, frame_shards, latent):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    import guidance_worker
+    lat, sched, guid = guidance_worker.main(frame_shards, latent)
+    q.put((rank, lat.numpy().copy(), sched, guid))             # by value (see test_host_emulated._worker)
+
+
+@pytest.mark.parametrize("frame_shards,latent", [(None, 8), (2, 16)])
+def test_two_gloo_ranks_are_bit_identical_to_one_process(emulated, frame_shards, latent):
+    """F = 14, windows 8 / 2, guidance_rescale = 0.7, guidance_end = 0.6 (3 guided + 2 unguided DDIM steps): the partials
+    of the rescale do not depend on the rank or granule a frame came from, so two gloo ranks (whole units, and every
+    unit frame-sharded two ways) give the bits of one process, on both ranks."""
+    import guidance_worker
+    ref, _, _ = guidance_worker.run(None, latent)
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, q, frame_shards, latent)) for r in range(2)]
+    for p in procs:
+        p.start()
+    results = [q.get(timeout=900) for _ in procs]
+    for p in procs:
+        p.join(timeout=120)
+        assert p.exitcode == 0
+    for rank, lat, sched, guid in results:
+        lat = torch.from_numpy(lat)
+        assert torch.isfinite(lat).all() and torch.equal(lat, ref), (rank, rel_l2(lat, ref))
+        assert sched["frame_shards"] == (frame_shards or 1) and sched["units"] == 4 and sched["world"] == 2
+        assert guid["unguided_schedule"]["units"] == 2 and guid["guided_steps"] == 3

@@ -4,11 +4,15 @@ with a chosen sampler and step count (GPU box):
     python tools/sampler_bench.py --scheduler dpm --steps 15 [--order 2]
     python tools/sampler_bench.py --scheduler euler-a --steps 25
     python tools/sampler_bench.py --scheduler ddim-eta --eta 1.0 --steps 25
+    python tools/sampler_bench.py --scheduler ddim --steps 25 --guidance-rescale 0.7 --guidance-end 0.6
 Prints one JSON line: ms per clip (host clock around whole clips, ending in a device synchronise), the denoise and decode
 milliseconds of the same clips (HIP events), and the average microseconds of the per-step update launch (HIP events
 around each `ops.overlap_ddim_step` / `ops.overlap_multistep_step` / `ops.overlap_ancestral_step` of one further,
 instrumented clip; for the ancestral samplers also `ddim_update_us`, the DDIM update of the same clip timed the same way,
-for comparison)."""
+for comparison).  The guidance controls (--guidance-rescale, --guidance-start, --guidance-end) are passed to the loop; the
+line then also carries them, the number of guided steps, `rescale_us` (the `ops.guidance_rescale` launches of a step,
+timed the same way; it stands in for the one `vx_combine_units` launch of a step without the rescale, `combine_us`) and
+the smallest and largest clip of the timed ones (`clip_ms_min`, `clip_ms_max`: HIP events, denoise + decode)."""
 import argparse
 import json
 import os
@@ -26,6 +30,9 @@ def main():
     ap.add_argument("--eta", type=float, default=1.0, help="DDIM eta of --scheduler ddim-eta")
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--order", type=int, choices=(1, 2), default=2, help="DPM-Solver++ solver_order")
+    ap.add_argument("--guidance-rescale", type=float, default=0.0, help="phi of the CFG rescale")
+    ap.add_argument("--guidance-start", type=float, default=0.0)
+    ap.add_argument("--guidance-end", type=float, default=1.0)
     ap.add_argument("--clips", type=int, default=5, help="timed clips")
     ap.add_argument("--warmup", type=int, default=1)
     args = ap.parse_args()
@@ -78,7 +85,9 @@ def main():
         lat = inp["latents"] * pipe.scheduler.init_noise_sigma     # (1 but for Euler ancestral)
         if ev:
             ev[0].record()
-        pipe.denoise(lat, kps_tokens, audio, timesteps, windows, 3.5, eta=eta, noise_seed=12345)
+        pipe.denoise(lat, kps_tokens, audio, timesteps, windows, 3.5, eta=eta, noise_seed=12345,
+                     guidance_rescale=args.guidance_rescale, guidance_start=args.guidance_start,
+                     guidance_end=args.guidance_end)
         if ev:
             ev[1].record()
         video = pipe.decode_latents(lat)
@@ -97,6 +106,7 @@ def main():
     clip_ms = 1e3 * (time.perf_counter() - t0) / args.clips
     denoise_ms = sum(e[0].elapsed_time(e[1]) for e in evs) / args.clips
     decode_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / args.clips
+    per_clip = [e[0].elapsed_time(e[2]) for e in evs]
     assert video.shape == (1, 3, F, 512, 512) and torch.isfinite(video).all()
     # one more clip with events around every update launch (kept out of the timed clips above)
     def update_launch_us(name):
@@ -116,6 +126,9 @@ def main():
         torch.cuda.synchronize()
         return len(marks), 1e3 * sum(s.elapsed_time(e) for s, e in marks) / len(marks)
     n_updates, update_us = update_launch_us(update)
+    guided = pipe.last_guidance["guided_steps"]
+    rescale_us = round(update_launch_us("guidance_rescale")[1], 2) if args.guidance_rescale > 0 and guided else None
+    combine_us = round(update_launch_us("combine_units")[1], 2) if rescale_us is None or guided < args.steps else None
     ddim_us = None
     if update == "overlap_ancestral_step":
         # the DDIM update of the same clip, timed the same way (eta = 0 on a DDIM scheduler of the same steps)
@@ -132,7 +145,9 @@ def main():
         config="512x512, 16 frames (one window), CFG 3.5, synthetic weights, bf16", clips=args.clips,
         ms_per_clip=round(clip_ms, 2), denoise_ms=round(denoise_ms, 2), decode_ms=round(decode_ms, 2),
         frames_per_s=round(F * 1e3 / clip_ms, 3), update_launches=n_updates, update_us=round(update_us, 2),
-        ddim_update_us=ddim_us)))
+        ddim_update_us=ddim_us, guidance_rescale=args.guidance_rescale, guidance_start=args.guidance_start,
+        guidance_end=args.guidance_end, guided_steps=guided, rescale_us=rescale_us, combine_us=combine_us,
+        clip_ms_min=round(min(per_clip), 2), clip_ms_max=round(max(per_clip), 2), build=vx.lib.lib.vx_build_id().decode())))
 
 
 if __name__ == "__main__":

@@ -126,6 +126,124 @@ __global__ void combine_units_kernel(const float* __restrict__ gathered, const i
     preds[(((size_t)wi * c + ch) * f + li) * hw + px] = u[ch] + guidance * (cnd[ch] - u[ch]);
 }
 
+// CFG rescale (Lin et al. 2024, diffusers rescale_noise_cfg): per window, g = u + s (c - u) scaled by
+// 1 + phi (std(c) / std(g) - 1), std the unbiased one over the window's c * f * hw values.  Two launches.
+// (1) guidance_stats_kernel: one block per (window, frame of the window, chunk of GR_CHUNK pixels) forms the block's
+// (count, mean, M2) of c and of g in two passes (sum -> mean, then sum of squared deviations from that mean) and writes
+// the six floats to its own place of the workspace: no atomics, and the block partition does not depend on where a frame
+// came from (granules, ranks) or on the number of windows.  (2) guidance_scale_kernel: merges a window's partials in
+// ascending (frame, chunk) order with the pairwise formula in double precision, then writes g * factor.
+constexpr int GR_CHUNK = 1024;   // pixels per partial
+constexpr int GR_THREADS = 256;
+
+__device__ __forceinline__ float cfg_mix(float u, float cnd, float guidance) { return u + guidance * (cnd - u); }
+
+// sum of (a, b) over the block: wave-64 shuffles, then LDS across the waves, added in wave order; every thread gets it
+__device__ __forceinline__ void block_sum2(float& a, float& b, float* lds) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_xor(a, off, 64);
+    b += __shfl_xor(b, off, 64);
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();                       // the previous use of lds is over
+  if (lane == 0) {
+    lds[2 * wave] = a;
+    lds[2 * wave + 1] = b;
+  }
+  __syncthreads();
+  a = lds[0];
+  b = lds[1];
+#pragma unroll
+  for (int w = 1; w < GR_THREADS / 64; ++w) {
+    a += lds[2 * w];
+    b += lds[2 * w + 1];
+  }
+}
+
+__global__ __launch_bounds__(GR_THREADS) void guidance_stats_kernel(const float* __restrict__ gathered,
+                                                                    const int32_t* __restrict__ unit_index, int shards,
+                                                                    int c, int f, int f_loc, int hw, int chunks,
+                                                                    float guidance, float* __restrict__ partials) {
+  __shared__ float lds[2 * (GR_THREADS / 64)];
+  const int chunk = blockIdx.x % chunks;
+  const int li = (blockIdx.x / chunks) % f;
+  const int wi = blockIdx.x / (chunks * f);
+  const int j = li / f_loc;
+  const long unit_sz = (long)f_loc * hw * c;
+  const float* ub = gathered + unit_index[(wi * 2 + 0) * shards + j] * unit_sz + (long)(li - j * f_loc) * hw * c;
+  const float* cb = gathered + unit_index[(wi * 2 + 1) * shards + j] * unit_sz + (long)(li - j * f_loc) * hw * c;
+  const int px0 = chunk * GR_CHUNK;
+  const int px1 = min(px0 + GR_CHUNK, hw);
+  const float n = (float)(px1 - px0) * (float)c;
+  float sc = 0.f, sg = 0.f;
+  for (int px = px0 + threadIdx.x; px < px1; px += GR_THREADS)
+    for (int ch = 0; ch < c; ++ch) {
+      const float u = ub[(long)px * c + ch], cnd = cb[(long)px * c + ch];
+      sc += cnd;
+      sg += cfg_mix(u, cnd, guidance);
+    }
+  block_sum2(sc, sg, lds);
+  const float mc = sc / n, mg = sg / n;
+  float qc = 0.f, qg = 0.f;
+  for (int px = px0 + threadIdx.x; px < px1; px += GR_THREADS)
+    for (int ch = 0; ch < c; ++ch) {
+      const float u = ub[(long)px * c + ch], cnd = cb[(long)px * c + ch];
+      const float dc = cnd - mc, dg = cfg_mix(u, cnd, guidance) - mg;
+      qc += dc * dc;
+      qg += dg * dg;
+    }
+  block_sum2(qc, qg, lds);
+  if (threadIdx.x == 0) {
+    float* p = partials + (size_t)blockIdx.x * 6;
+    p[0] = n; p[1] = mc; p[2] = qc;
+    p[3] = n; p[4] = mg; p[5] = qg;
+  }
+}
+
+__global__ __launch_bounds__(GR_THREADS) void guidance_scale_kernel(const float* __restrict__ gathered,
+                                                                    const int32_t* __restrict__ unit_index, int shards,
+                                                                    int c, int f, int f_loc, int hw, int parts,
+                                                                    float guidance, float phi,
+                                                                    const float* __restrict__ partials,
+                                                                    float* __restrict__ preds) {
+  __shared__ float factor_s;
+  const int wi = blockIdx.y;
+  if (threadIdx.x == 0) {
+    float factor = 1.f;
+    if (phi != 0.f) {
+      const float* p = partials + (size_t)wi * parts * 6;
+      double n = 0.0, mean[2] = {0.0, 0.0}, m2[2] = {0.0, 0.0};
+      for (int k = 0; k < parts; ++k) {                       // ascending (frame, chunk)
+        const double nb = p[k * 6];
+        const double nn = n + nb;
+        for (int t = 0; t < 2; ++t) {
+          const double delta = (double)p[k * 6 + 3 * t + 1] - mean[t];
+          mean[t] += delta * (nb / nn);
+          m2[t] += (double)p[k * 6 + 3 * t + 2] + delta * delta * (n * nb / nn);
+        }
+        n = nn;
+      }
+      // std(c) / std(g): the n - 1 of both cancels
+      factor = (float)(1.0 + (double)phi * (sqrt(m2[0] / m2[1]) - 1.0));
+    }
+    factor_s = factor;
+  }
+  __syncthreads();
+  const float factor = factor_s;
+  const long idx = (long)blockIdx.x * GR_THREADS + threadIdx.x;   // (li, pixel) of window wi
+  if (idx >= (long)f * hw) return;
+  const int px = (int)(idx % hw);
+  const int li = (int)(idx / hw);
+  const int j = li / f_loc;
+  const long row = (long)(li - j * f_loc) * hw + px;
+  const long unit_sz = (long)f_loc * hw * c;
+  const float* u = gathered + unit_index[(wi * 2 + 0) * shards + j] * unit_sz + row * c;
+  const float* cnd = gathered + unit_index[(wi * 2 + 1) * shards + j] * unit_sz + row * c;
+  for (int ch = 0; ch < c; ++ch)
+    preds[(((size_t)wi * c + ch) * f + li) * hw + px] = cfg_mix(u[ch], cnd[ch], guidance) * factor;
+}
+
 __global__ void overlap_ddim_kernel(float* latents, int c, int total_frames, int hw, const float* preds, int f_window,
                                     const int32_t* terms, int max_terms, const int32_t* frame_ids,
                                     const float* count, int n_frames, float sqrt_a, float sqrt_1ma,
@@ -424,6 +542,36 @@ extern "C" int vx_combine_units(const float* gathered, const int32_t* unit_index
   hipLaunchKernelGGL(combine_units_kernel, grid1d((long)n_windows * f * hw), dim3(256), 0, (hipStream_t)stream,
                      gathered, unit_index, n_windows, halves, shards, c, f, f / shards, hw, guidance, preds);
   return vx_check_launch("vx_combine_units");
+}
+
+extern "C" int64_t vx_guidance_rescale_ws_floats(int n_windows, int f, int hw) {
+  if (n_windows <= 0 || f <= 0 || hw <= 0) return 0;
+  return (int64_t)n_windows * f * ((hw + GR_CHUNK - 1) / GR_CHUNK) * 6;
+}
+
+extern "C" int vx_guidance_rescale(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c,
+                                   int f, int hw, float guidance, float phi, float* workspace, int64_t ws_floats,
+                                   float* preds, void* stream) {
+  VX_REQUIRE(gathered && unit_index && workspace && preds && n_windows > 0 && n_windows <= 65535 && shards > 0 && c > 0 &&
+                 f > 0 && hw > 0 && f % shards == 0,
+             "vx_guidance_rescale: bad arguments");
+  VX_REQUIRE(phi >= 0.f && phi <= 1.f, "vx_guidance_rescale: phi must lie in [0, 1]");
+  VX_REQUIRE((long)c * f * hw >= 2, "vx_guidance_rescale: the standard deviation needs two values per window");
+  VX_REQUIRE(ws_floats >= vx_guidance_rescale_ws_floats(n_windows, f, hw),
+             "vx_guidance_rescale: workspace too small (vx_guidance_rescale_ws_floats)");
+  const int chunks = (hw + GR_CHUNK - 1) / GR_CHUNK;
+  VX_REQUIRE((long)n_windows * f * chunks <= 0x7fffffffL, "vx_guidance_rescale: too many partials");
+  if (phi != 0.f) {
+    hipLaunchKernelGGL(guidance_stats_kernel, dim3((unsigned)(n_windows * f * chunks)), dim3(GR_THREADS), 0,
+                       (hipStream_t)stream, gathered, unit_index, shards, c, f, f / shards, hw, chunks, guidance,
+                       workspace);
+    int rc = vx_check_launch("vx_guidance_rescale (statistics)");
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(guidance_scale_kernel, dim3((unsigned)(((long)f * hw + GR_THREADS - 1) / GR_THREADS), n_windows),
+                     dim3(GR_THREADS), 0, (hipStream_t)stream, gathered, unit_index, shards, c, f, f / shards, hw,
+                     f * chunks, guidance, phi, workspace, preds);
+  return vx_check_launch("vx_guidance_rescale");
 }
 
 extern "C" int vx_overlap_ddim_step(float* latents, int c, int total_frames, int hw, const float* preds, int f_window,

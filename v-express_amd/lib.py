@@ -159,6 +159,9 @@ def _load(path=None, element="bf16"):
     lib.vx_cfg_combine.argtypes = [vp, i32, i32, i32, i32, f32, vp, vp]
     lib.vx_pack_rows.argtypes = [vp, i32, i64, i32, vp, vp]
     lib.vx_combine_units.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp]
+    lib.vx_guidance_rescale_ws_floats.restype = i64
+    lib.vx_guidance_rescale_ws_floats.argtypes = [i32, i32, i32]
+    lib.vx_guidance_rescale.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, i64, vp, vp]
     lib.vx_overlap_ddim_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, f32, f32, f32, f32, vp]
     lib.vx_overlap_multistep_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, f32, f32, f32, f32,
                                               f32, vp]
@@ -171,7 +174,8 @@ def _load(path=None, element="bf16"):
     lib.vx_wave_conv1d.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp]
     for name in declared_symbols():
         fn = getattr(lib, name)
-        if name not in ("vx_last_error_string", "vx_groupnorm_ws_floats", "vx_gemm_config_name",
+        if name not in ("vx_last_error_string", "vx_groupnorm_ws_floats", "vx_guidance_rescale_ws_floats",
+                        "vx_gemm_config_name",
                         "vx_gemm_splitk_ws_bytes", "vx_gemm_last_kernel", "vx_last_kernel", "vx_build_id",
                         "vx_tblock_packed_bytes", "vx_element_type", "vx_audio_xattn_packed_bytes"):
             fn.restype = i32

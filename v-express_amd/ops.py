@@ -1333,6 +1333,34 @@ def combine_units(gathered, unit_index, c, f, hw, guidance, preds):
                                   _ptr(preds), _stream()), "vx_combine_units")
 
 
+def guidance_rescale_ws_floats(nW, f, hw):
+    """float32 elements of the workspace `guidance_rescale` needs for nW windows of f frames of hw pixels."""
+    return int(_lib.vx_guidance_rescale_ws_floats(int(nW), int(f), int(hw)))
+
+
+def guidance_rescale(gathered, unit_index, c, f, hw, guidance, phi, workspace, preds):
+    """`combine_units` with the CFG rescale of diffusers' rescale_noise_cfg: gathered fp32 [units_total, (f/S)*hw, c],
+    unit_index int32 [nW, 2, S] -> preds fp32 [nW, c, f, hw] = g * (1 + phi (std(cond) / std(g) - 1)) per window,
+    g = u + guidance (cond - u); workspace: float32, at least guidance_rescale_ws_floats(nW, f, hw) elements."""
+    if unit_index.dim() != 3 or unit_index.shape[1] != 2:
+        raise ValueError("guidance_rescale: unit_index must be [nW, 2, S] (both CFG halves)")
+    nW, _, S = unit_index.shape
+    if unit_index.dtype != torch.int32 or not unit_index.is_contiguous() or not gathered.is_contiguous():
+        raise TypeError("guidance_rescale: contiguous int32 index / contiguous gathered buffer expected")
+    if (gathered.dtype != torch.float32 or preds.dtype != torch.float32 or workspace.dtype != torch.float32
+            or not preds.is_contiguous() or not workspace.is_contiguous()):
+        raise TypeError("guidance_rescale: contiguous float32 gathered / workspace / preds expected")
+    if f % S or gathered.numel() % ((f // S) * hw * c) or preds.numel() != nW * c * f * hw:
+        raise ValueError("guidance_rescale: buffer sizes do not match (nW, c, f, hw, S)")
+    if not 0.0 <= float(phi) <= 1.0:
+        raise ValueError(f"guidance_rescale: phi must lie in [0, 1], got {phi}")
+    if workspace.numel() < guidance_rescale_ws_floats(nW, f, hw):
+        raise ValueError("guidance_rescale: workspace smaller than guidance_rescale_ws_floats(nW, f, hw)")
+    L.check(_lib.vx_guidance_rescale(_ptr(gathered), _ptr(unit_index), nW, S, c, f, hw, float(guidance), float(phi),
+                                     _ptr(workspace), workspace.numel(), _ptr(preds), _stream()),
+            "vx_guidance_rescale")
+
+
 def overlap_ddim_step(latents, preds, terms, frame_ids, counts, coef):
     """latents fp32 [1,C,F,h,w] updated in place for `frame_ids`; preds fp32 [slots, C, f, hw]."""
     _, c, F, h, w = latents.shape

@@ -54,6 +54,24 @@ def _pipeline_element(pipe):
     return L.ELEM[0]
 
 
+def guided_steps(n, guidance_start=0.0, guidance_end=1.0):
+    """Which of n timesteps run with classifier-free guidance: step i iff i / n >= start and (i + 1) / n <= end
+    (diffusers' control_guidance_start / _end rule, in Python floats)."""
+    return [i / n >= guidance_start and (i + 1) / n <= guidance_end for i in range(n)]
+
+
+def check_guidance(guidance_rescale, guidance_start, guidance_end, n):
+    """Validates the guidance controls; returns (phi as float, guided_steps(n, start, end))."""
+    phi, start, end = float(guidance_rescale), float(guidance_start), float(guidance_end)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"guidance_rescale must lie in [0, 1], got {guidance_rescale}")
+    if not (0.0 <= start <= 1.0 and 0.0 <= end <= 1.0):
+        raise ValueError(f"guidance_start / guidance_end must lie in [0, 1], got {guidance_start} / {guidance_end}")
+    if start > end:
+        raise ValueError(f"guidance_start ({guidance_start}) must not exceed guidance_end ({guidance_end})")
+    return phi, guided_steps(n, start, end)
+
+
 class VExpressPipeline:
     def __init__(self, vae, reference_net, denoising_unet, v_kps_guider=None, audio_processor=None,
                  audio_encoder=None, audio_projection=None, scheduler=None, image_proj_model=None, tokenizer=None,
@@ -77,6 +95,9 @@ class VExpressPipeline:
         self.mixed_shards = None
         # the schedule the last denoise() call chose (for logs / bench.py): dict(kind, frame_shards, mixed_shards, ...)
         self.last_schedule = {}
+        # the guidance controls of the last denoise() call: dict(guided_steps, steps, rescale, unguided_schedule), the
+        # last one the last_schedule-style dict of the conditional-only plan of its unguided steps, or None
+        self.last_guidance = {}
         # batch rows per UNet call: 2 = the two CFG halves of one window; 4 (default), 6, ... also merge consecutive
         # windows of this rank into one call.  Every kernel is batch-invariant, so the rows come out bit-identical;
         # merged calls measure 4-5 % faster (profiles/r02e_host_overhead.json: b = 3 74.0 ms vs 49.2 + 28.2 ms,
@@ -217,53 +238,19 @@ class VExpressPipeline:
             return [self.scheduler.ancestral_coefficients(t, eta) for t in timesteps]
         return [self.scheduler.ancestral_coefficients(begin_index + i) for i in range(len(timesteps))]
 
-    @_in_unet_element_type
-    def denoise(self, latents, kps_tokens, audio, timesteps, windows, guidance_scale, callback=None,
-                callback_steps=1, *, begin_index=None, eta=0.0, noise_seed=None):
-        """pipelines/v_express_pipeline.py:526-583.  latents fp32 [1,4,F,h,w] (device, updated in place);
-        kps_tokens bf16 [b, F, hw, C0]; audio bf16 [b, F, n_ctx, 768] with b = 2 (uncond, cond) under classifier-free
-        guidance (guidance_scale > 1, :443) and b = 1 (the conditional row only) without.
-        DPM-Solver++ and the ancestral samplers: `timesteps` are the scheduler's from step index `begin_index` on
-        (default: its last len(timesteps)); each frame gets exactly one update per timestep, so the multistep history is
-        per frame.  Ancestral samplers (DDIM with eta > 0, Euler ancestral) draw the noise of step index i on the device
-        from `noise_seed` (64 bits, required), keyed by (step index, frame, channel, pixel) only.  Euler ancestral: the
-        latents come and go in the scheduler's (VE) frame; the loop runs in the VP frame x / sqrt(1 + sigma^2)."""
-        kind = self._sampler(eta)
-        if kind != "ddim":
-            all_ts = [int(t) for t in self.scheduler.timesteps.tolist()]
-            if begin_index is None:
-                begin_index = len(all_ts) - len(timesteps)
-            if [int(t) for t in timesteps] != all_ts[begin_index:begin_index + len(timesteps)]:
-                raise ValueError(f"{type(self.scheduler).__name__}: timesteps must be the scheduler's own, from step "
-                                 f"index begin_index on")
-        ancestral = kind in ("ddim-eta", "euler-a")
-        if ancestral and noise_seed is None:
-            raise ValueError(f"the {kind} sampler draws noise on the device: pass noise_seed")
-        multistep = kind == "dpm"
+    def _unit_plan(self, latents, kps_tokens, audio, audio_is_zero, windows, win_ids, half_rows):
+        """The static plan of one kind of timestep: which (window, half) units this rank computes, in which UNet calls,
+        and where they land in the exchange buffer.  `half_rows`: the row of the kps / audio tensors and of the reference
+        banks that each half of the plan uses - [0, 1] under classifier-free guidance, [0] without, [1] for the
+        conditional half alone of a CFG clip (an unguided step).  Collective (`dc.frame_shard`): every rank builds it.
+        Returns dict(calls, local, uidx, max_slots, schedule)."""
         unet, dc, dev = self.denoising_unet, self.dist, latents.device
         _, C, F, H, W = latents.shape
         hw = H * W
         f = len(windows[0])
-        if any(len(w) != f for w in windows):
-            raise ValueError("all context windows must have the same length")
         nW = len(windows)
-        plan = overlap_plan(windows, F)
-        win_ids = torch.tensor(windows, dtype=torch.int32, device=dev)
+        halves_n = len(half_rows)
         win_ids_long = win_ids.long()
-        sf = plan["step_frames"]
-        terms = torch.full((len(sf), plan["max_terms"], 2), -1, dtype=torch.int32)
-        for i, fr in enumerate(sf):
-            for j, (wi, li) in enumerate(plan["terms"][fr]):
-                terms[i, j, 0], terms[i, j, 1] = wi, li
-        terms = terms.to(dev)
-        frame_ids = torch.tensor(sf, dtype=torch.int32, device=dev)
-        counts = torch.tensor([float(plan["counts"][fr]) for fr in sf], dtype=torch.float32, device=dev)
-        # work units of this rank; S > 1: the window's frames are split over S ranks per unit (short clips)
-        do_cfg = guidance_scale > 1.0
-        halves_n = 2 if do_cfg else 1
-        if kps_tokens.shape[0] != halves_n or audio.shape[0] != halves_n:
-            raise ValueError(f"guidance_scale={guidance_scale} needs {halves_n} batch row(s) of kps features / audio "
-                             f"embeddings, got {kps_tokens.shape[0]} / {audio.shape[0]}")
         min_hw = (H // 8) * (W // 8)
         S = self.frame_shards or choose_frame_shards(nW, dc.world_size, f, min_hw, halves_n)
         if S < 1 or dc.world_size % S or f % S or min_hw % S:
@@ -277,8 +264,8 @@ class VExpressPipeline:
         whole_units_only = self.mixed_shards == 1 or (self.frame_shards == 1 and self.mixed_shards is None)
         if S == 1 and dc.enabled and not whole_units_only:
             Sm = self.mixed_shards or choose_mixed_shards(nW * halves_n, dc.world_size, f, min_hw)
-        self.last_schedule = dict(kind="mixed" if Sm > 1 else ("frame-sharded" if S > 1 else "whole units"),
-                                  frame_shards=S, mixed_shards=Sm, units=nW * halves_n, world=dc.world_size)
+        schedule = dict(kind="mixed" if Sm > 1 else ("frame-sharded" if S > 1 else "whole units"),
+                        frame_shards=S, mixed_shards=Sm, units=nW * halves_n, world=dc.world_size)
         if Sm > 1:
             sched_m = MixedUnitSchedule(nW, dc.world_size, Sm, halves_n)
             G, max_slots, unit_slots = Sm, sched_m.max_slots, sched_m.slots
@@ -297,7 +284,6 @@ class VExpressPipeline:
         # per-timestep exchange: only conv_out's C real channels travel (the GEMM pads them to 8); unit_index tells the
         # combine kernel which gathered slot holds frame granule j of (window, CFG half)
         local = torch.zeros((max_slots, g_frames * hw, C), device=dev, dtype=torch.float32)
-        preds = torch.empty((nW, C, f, hw), device=dev, dtype=torch.float32)
         uidx = torch.empty((nW, halves_n, G), dtype=torch.int32)
         for wi in range(nW):
             for hlf in range(halves_n):
@@ -306,8 +292,6 @@ class VExpressPipeline:
         uidx = uidx.to(dev)
         # per-call constants (window ids, conditioning slices) do not depend on the timestep: build them once so
         # the timestep loop issues kernels only (no host->device copies, no syncs)
-        # which CFG halves carry all-zero audio tokens (the unconditional half, :403-405): one device reduction per clip
-        audio_is_zero = [bool((audio[hh] == 0).all().item()) for hh in range(audio.shape[0])]
         # UNet calls of this rank: the units of one window always share a call; `units_per_call` > 2 also merges
         # consecutive windows into one batch (every kernel is batch-invariant, so the rows come out identical - only
         # the launches get fatter, which helps the 16x16 / 8x8 levels of multi-window clips)
@@ -329,7 +313,7 @@ class VExpressPipeline:
                 rows = [(wi, hlf) for wi, halves in group for hlf in halves]      # batch rows of the call, in order
                 kps_l, ehs_l = [], []
                 for wi, halves in group:
-                    hsel = torch.tensor(halves, device=dev)
+                    hsel = torch.tensor([half_rows[hlf] for hlf in halves], device=dev)
                     ids_long = win_ids_long[wi][lo:lo + f_loc]
                     kps_l.append(kps_tokens.index_select(0, hsel).index_select(1, ids_long)
                                  .reshape(len(halves) * f_loc, hw, -1))
@@ -343,7 +327,80 @@ class VExpressPipeline:
                 s0 = min(slot for (r, slot) in unit_slots[rows[0]] if r == dc.rank)
                 n_slots = len(rows) * (G // Sc)
                 # the audio K | V of all 16 transformer blocks is step-invariant: once per clip and call
-                calls.append((rows, gathers, kps, ehs, unet.precompute_audio_kv(ehs), f_loc, shard, s0, n_slots))
+                bank_rows = [half_rows[hlf] for _, hlf in rows]
+                calls.append((bank_rows, gathers, kps, ehs, unet.precompute_audio_kv(ehs),
+                              [audio_is_zero[r] for r in bank_rows], f_loc, shard, s0, n_slots))
+        return dict(calls=calls, local=local, uidx=uidx, max_slots=max_slots, schedule=schedule)
+
+    @_in_unet_element_type
+    def denoise(self, latents, kps_tokens, audio, timesteps, windows, guidance_scale, callback=None,
+                callback_steps=1, *, begin_index=None, eta=0.0, noise_seed=None, guidance_rescale=0.0,
+                guidance_start=0.0, guidance_end=1.0):
+        """pipelines/v_express_pipeline.py:526-583.  latents fp32 [1,4,F,h,w] (device, updated in place);
+        kps_tokens bf16 [b, F, hw, C0]; audio bf16 [b, F, n_ctx, 768] with b = 2 (uncond, cond) under classifier-free
+        guidance (guidance_scale > 1, :443) and b = 1 (the conditional row only) without.
+        DPM-Solver++ and the ancestral samplers: `timesteps` are the scheduler's from step index `begin_index` on
+        (default: its last len(timesteps)); each frame gets exactly one update per timestep, so the multistep history is
+        per frame.  Ancestral samplers (DDIM with eta > 0, Euler ancestral) draw the noise of step index i on the device
+        from `noise_seed` (64 bits, required), keyed by (step index, frame, channel, pixel) only.  Euler ancestral: the
+        latents come and go in the scheduler's (VE) frame; the loop runs in the VP frame x / sqrt(1 + sigma^2).
+        Guidance controls (classifier-free guidance only; every sampler): step i of the N timesteps is guided iff
+        i / N >= guidance_start and (i + 1) / N <= guidance_end, any other step computes the conditional rows only and
+        takes them as the prediction; guidance_rescale = phi > 0 scales each window's guided prediction g by
+        1 + phi (std(cond) / std(g) - 1) before the overlap sum (diffusers' rescale_noise_cfg, vx_guidance_rescale)."""
+        kind = self._sampler(eta)
+        guidance_rescale, guided = check_guidance(guidance_rescale, guidance_start, guidance_end, len(timesteps))
+        if kind != "ddim":
+            all_ts = [int(t) for t in self.scheduler.timesteps.tolist()]
+            if begin_index is None:
+                begin_index = len(all_ts) - len(timesteps)
+            if [int(t) for t in timesteps] != all_ts[begin_index:begin_index + len(timesteps)]:
+                raise ValueError(f"{type(self.scheduler).__name__}: timesteps must be the scheduler's own, from step "
+                                 f"index begin_index on")
+        ancestral = kind in ("ddim-eta", "euler-a")
+        if ancestral and noise_seed is None:
+            raise ValueError(f"the {kind} sampler draws noise on the device: pass noise_seed")
+        multistep = kind == "dpm"
+        unet, dc, dev = self.denoising_unet, self.dist, latents.device
+        _, C, F, H, W = latents.shape
+        hw = H * W
+        f = len(windows[0])
+        if any(len(w) != f for w in windows):
+            raise ValueError("all context windows must have the same length")
+        nW = len(windows)
+        plan = overlap_plan(windows, F)
+        win_ids = torch.tensor(windows, dtype=torch.int32, device=dev)
+        sf = plan["step_frames"]
+        terms = torch.full((len(sf), plan["max_terms"], 2), -1, dtype=torch.int32)
+        for i, fr in enumerate(sf):
+            for j, (wi, li) in enumerate(plan["terms"][fr]):
+                terms[i, j, 0], terms[i, j, 1] = wi, li
+        terms = terms.to(dev)
+        frame_ids = torch.tensor(sf, dtype=torch.int32, device=dev)
+        counts = torch.tensor([float(plan["counts"][fr]) for fr in sf], dtype=torch.float32, device=dev)
+        do_cfg = guidance_scale > 1.0
+        halves_n = 2 if do_cfg else 1
+        if kps_tokens.shape[0] != halves_n or audio.shape[0] != halves_n:
+            raise ValueError(f"guidance_scale={guidance_scale} needs {halves_n} batch row(s) of kps features / audio "
+                             f"embeddings, got {kps_tokens.shape[0]} / {audio.shape[0]}")
+        if not do_cfg:                                # nothing to rescale, nothing to switch off
+            guidance_rescale, guided = 0.0, [True] * len(timesteps)
+        # which CFG halves carry all-zero audio tokens (the unconditional half, :403-405): one device reduction per clip
+        audio_is_zero = [bool((audio[hh] == 0).all().item()) for hh in range(audio.shape[0])]
+        # one plan for the guided steps (every step, by default); a second one, the conditional half alone, only when
+        # some step runs without guidance.  Both are built on every rank, before the loop (the shard groups are collective)
+        preds = torch.empty((nW, C, f, hw), device=dev, dtype=torch.float32)
+        plan_g = self._unit_plan(latents, kps_tokens, audio, audio_is_zero, windows, win_ids, list(range(halves_n)))
+        self.last_schedule = plan_g["schedule"]
+        plan_c = None
+        if not all(guided):
+            plan_c = self._unit_plan(latents, kps_tokens, audio, audio_is_zero, windows, win_ids, [1])
+        self.last_guidance = dict(guided_steps=sum(guided) if do_cfg else 0, steps=len(timesteps),
+                                  rescale=guidance_rescale,
+                                  unguided_schedule=None if plan_c is None else plan_c["schedule"])
+        rescale_ws = None
+        if guidance_rescale > 0.0 and any(guided):
+            rescale_ws = torch.empty(ops.guidance_rescale_ws_floats(nW, f, hw), device=dev, dtype=torch.float32)
         # DPM-Solver++: the previous step's x0 of every frame (identical on every rank, like the latents) and the
         # update coefficients of every step, resolved on the host before the loop
         x0_hist = torch.empty_like(latents) if multistep else None
@@ -357,17 +414,23 @@ class VExpressPipeline:
             latents.mul_(1.0 / self.scheduler.frame_scale(begin_index))          # VE -> VP, once
         for i, t in enumerate(timesteps):
             t = int(t)
-            for rows, gathers, kps, ehs, akv, f_loc, shard, s0, n_slots in calls:
+            step_plan = plan_g if guided[i] else plan_c
+            local, max_slots, uidx = step_plan["local"], step_plan["max_slots"], step_plan["uidx"]
+            for bank_rows, gathers, kps, ehs, akv, azero, f_loc, shard, s0, n_slots in step_plan["calls"]:
                 parts = [ops.gather_latents(latents, ids, reps=reps) for ids, reps in gathers]
                 x_in = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
-                out = unet.forward_tokens(x_in, t, ehs, kps, b=len(rows), f=f_loc, H=H, W=W,
-                                          batch_rows=[hlf for _, hlf in rows], audio_kv=akv,
-                                          audio_zero=[audio_is_zero[hlf] for _, hlf in rows], frame_shard=shard)
+                out = unet.forward_tokens(x_in, t, ehs, kps, b=len(bank_rows), f=f_loc, H=H, W=W,
+                                          batch_rows=bank_rows, audio_kv=akv, audio_zero=azero, frame_shard=shard)
                 # a call's units occupy consecutive send slots, in row order: one strided pack per call
                 ops.pack_rows(out, C, local[s0:s0 + n_slots])
             gathered = dc.all_gather_units(local, max_slots)          # [world, max_slots, (f/G)*hw, C]
-            # CFG combine of every window in one launch (:548-550; without CFG the prediction itself)
-            ops.combine_units(gathered, uidx, C, f, hw, guidance_scale if do_cfg else 1.0, preds)
+            if rescale_ws is not None and guided[i]:
+                # the CFG combine with each window's prediction rescaled towards the conditional one's spread
+                ops.guidance_rescale(gathered, uidx, C, f, hw, guidance_scale, guidance_rescale, rescale_ws, preds)
+            else:
+                # CFG combine of every window in one launch (:548-550; without CFG, and in an unguided step, the
+                # conditional prediction itself)
+                ops.combine_units(gathered, uidx, C, f, hw, guidance_scale if do_cfg and guided[i] else 1.0, preds)
             if multistep:
                 ops.overlap_multistep_step(latents, preds, terms, frame_ids, counts, x0_hist, coefs[i])
             elif ancestral:
@@ -415,9 +478,12 @@ class VExpressPipeline:
                  context_overlap=4, reference_attention_weight=1., audio_attention_weight=1.,
                  num_pad_audio_frames=2, do_multi_devices_inference=False, save_gpu_memory=False,
                  reference_latents=None, kps_features=None, audio_embeddings=None, latents=None,
-                 noise_seed: Optional[int] = None, output_device="cpu", decode=True, **kwargs):
-        # an unsupported scheduler, or eta with one other than DDIM, fails here, before the prologue
+                 noise_seed: Optional[int] = None, output_device="cpu", decode=True, guidance_rescale: float = 0.0,
+                 guidance_start: float = 0.0, guidance_end: float = 1.0, **kwargs):
+        # an unsupported scheduler, eta with one other than DDIM, or guidance controls out of range fail here, before
+        # the prologue
         kind = self._sampler(eta)
+        check_guidance(guidance_rescale, guidance_start, guidance_end, max(int(num_inference_steps), 1))
         dev = self.device
         do_cfg = guidance_scale > 1.0
         # timesteps (retrieve_timesteps + get_timesteps, :448-449)
@@ -474,7 +540,8 @@ class VExpressPipeline:
         if timed:
             ev[0].record()
         self.denoise(lat, kps_tokens, audio, timesteps, windows, guidance_scale, callback, callback_steps or 1,
-                     begin_index=begin_index, eta=eta, noise_seed=noise_seed)
+                     begin_index=begin_index, eta=eta, noise_seed=noise_seed, guidance_rescale=guidance_rescale,
+                     guidance_start=guidance_start, guidance_end=guidance_end)
         if timed:
             ev[1].record()
         reader.clear()
