@@ -454,6 +454,17 @@ int vx_overlap_ancestral_step(float* latents, int c, int total_frames, int hw, c
                               const int32_t* terms, int max_terms, const int32_t* frame_ids, const float* count,
                               int n_frames, float alpha_s, float sigma_s, float c_x, float c_0, float c_z,
                               uint32_t seed_lo, uint32_t seed_hi, int step_index, void* stream);
+/* Known-region blend of init-video sampling (img2img / inpainting for a 4-channel UNet):
+ *   mask != NULL:  latents = m * latents + (1 - m) * (a * init + s * noise)      (m = 1 regenerates, m = 0 keeps)
+ *   mask == NULL:  latents = a * init + s * noise                                (the start latents; the old value is not read)
+ * latents / init / noise: float32 [c, total_frames, hw]; mask: float32 [total_frames, hw] in [0, 1], shared by the
+ * channels; (a, s) >= 0 the signal / noise pair of the schedule level the latents are at.  One launch after the update
+ * of a timestep; at (a, s) = (1, 0) a cell with m = 0 receives init exactly and a cell with m = 1 keeps its bits.
+ * hw % 4 == 0; every pointer 16-byte aligned.  Replaces diffusers' StableDiffusionImg2ImgPipeline.prepare_latents
+ * (scheduler.add_noise) and the `(1 - init_mask) * init_latents_proper + init_mask * latents` of
+ * StableDiffusionInpaintPipeline.__call__'s loop; the reference has neither.  */
+int vx_known_blend(float* latents, const float* init, const float* noise, const float* mask, int c, int total_frames,
+                   int hw, float a, float s, void* stream);
 /* NCHW-ish float32 [b, C, f, h, w] -> NHWC bf16 [(b f), h*w, c_pad]  (API-boundary layout change) */
 int vx_ncfhw_to_nhwc(const float* x, int b, int c, int f, int hw, int c_pad, void* out, void* stream);
 /* NHWC float32 [(b f), hw, ld] -> [b, C, f, h*w] float32 */
@@ -461,6 +472,15 @@ int vx_nhwc_to_ncfhw(const float* x, int ld, int b, int c, int f, int hw, float*
 /* VAE post-process: NHWC float32 [n, hw, ld] -> clamp(x/2+0.5, 0, 1) as [n, 3, hw] float32
  * (pipelines/v_express_pipeline.py:160). */
 int vx_vae_postprocess(const float* x, int ld, int n, int c, int hw, float* out, void* stream);
+/* vx_vae_postprocess composited onto the footage the clip was started from, in one pass:
+ *   out[fr, ch, px] = M * clamp(x/2+0.5, 0, 1) + (1 - M) * init[ch, frame0 + fr, px]
+ * init: float32 [c, total_frames, hw] in [0, 1] (the caller's video, never through the VAE); mask: float32
+ * [mask_frames, hw] in [0, 1] at pixel resolution, mask_frames == total_frames or 1 (one mask for every frame); the n
+ * decoded frames are frames frame0 .. frame0 + n - 1 of the clip.  M = 1 writes the bits of vx_vae_postprocess, M = 0
+ * the bits of init.  Replaces diffusers' VaeImageProcessor.apply_overlay (a PIL paste per frame); the reference has no
+ * counterpart.  */
+int vx_vae_postprocess_composite(const float* x, int ld, int n, int c, int hw, const float* init, int total_frames,
+                                 int frame0, const float* mask, int mask_frames, float* out, void* stream);
 /* 3x3x3 median over (frame, y, x) with reflect padding + optional uint8 packing of the result.
  * Replaces pipelines/utils.py:46-61 (median_filter_3d, kernel_size 3) and the (video*255).astype(uint8) + HWC
  * permute of save_video (:70-73).  video: float32 [c, f, h, w]; out_f32: float32 [c, f, h, w] or NULL;

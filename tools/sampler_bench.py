@@ -5,6 +5,7 @@ with a chosen sampler and step count (GPU box):
     python tools/sampler_bench.py --scheduler euler-a --steps 25
     python tools/sampler_bench.py --scheduler ddim-eta --eta 1.0 --steps 25
     python tools/sampler_bench.py --scheduler ddim --steps 25 --guidance-rescale 0.7 --guidance-end 0.6
+    python tools/sampler_bench.py --scheduler ddim --steps 25 --init-video --strength 0.6 --mask lower-half
 Prints one JSON line: ms per clip (host clock around whole clips, ending in a device synchronise), the denoise and decode
 milliseconds of the same clips (HIP events), and the average microseconds of the per-step update launch (HIP events
 around each `ops.overlap_ddim_step` / `ops.overlap_multistep_step` / `ops.overlap_ancestral_step` of one further,
@@ -12,7 +13,12 @@ instrumented clip; for the ancestral samplers also `ddim_update_us`, the DDIM up
 for comparison).  The guidance controls (--guidance-rescale, --guidance-start, --guidance-end) are passed to the loop; the
 line then also carries them, the number of guided steps, `rescale_us` (the `ops.guidance_rescale` launches of a step,
 timed the same way; it stands in for the one `vx_combine_units` launch of a step without the rescale, `combine_us`) and
-the smallest and largest clip of the timed ones (`clip_ms_min`, `clip_ms_max`: HIP events, denoise + decode)."""
+the smallest and largest clip of the timed ones (`clip_ms_min`, `clip_ms_max`: HIP events, denoise + decode).
+--init-video starts every clip from a synthetic 16-frame video (VAE-encoded inside the clip: `encode_ms`, part of
+`denoise_ms` and of the clip) noised to the level of --strength, which also cuts the timesteps to the last
+int(steps * strength); --mask lower-half keeps the upper half of every frame (a `vx_known_blend` launch after every step,
+`blend_us`, and the composite post-process at the decode).  `postprocess_us` is the post-process launch of a decoded
+chunk (`postprocess`: which of the two ran), timed like the update launch."""
 import argparse
 import json
 import os
@@ -33,28 +39,40 @@ def main():
     ap.add_argument("--guidance-rescale", type=float, default=0.0, help="phi of the CFG rescale")
     ap.add_argument("--guidance-start", type=float, default=0.0)
     ap.add_argument("--guidance-end", type=float, default=1.0)
+    ap.add_argument("--init-video", action="store_true", help="start from a synthetic init video (img2img)")
+    ap.add_argument("--strength", type=float, default=1.0, help="run the last int(steps * strength) timesteps")
+    ap.add_argument("--mask", choices=("none", "lower-half"), default="none",
+                    help="with --init-video: regenerate the lower half of every frame, keep the upper half")
     ap.add_argument("--clips", type=int, default=5, help="timed clips")
     ap.add_argument("--warmup", type=int, default=1)
     args = ap.parse_args()
     if args.steps < 1 or args.clips < 1:
         ap.error("--steps and --clips must be >= 1")
+    if args.mask != "none" and not args.init_video:
+        ap.error("--mask needs --init-video")
+    if not 0.0 <= args.strength <= 1.0:
+        ap.error("--strength must lie in [0, 1]")
     if not torch.cuda.is_available():
         raise SystemExit("sampler_bench.py measures on the GPU: no device visible")
     import v_express_amd as vx
     from v_express_amd import ops, synth
     from v_express_amd.context import uniform
+    from v_express_amd.pipeline import latent_mask
     dev, elem = torch.device("cuda", 0), torch.bfloat16
     torch.cuda.set_device(dev)
     cfg, vcfg = synth.UNetConfig(), synth.VaeConfig()
     F, h = 16, 64
     unet = vx.UNet3DConditionModel(cfg).to(dev).to(elem)
     refnet = vx.UNet2DConditionModel(cfg).to(dev).to(elem)
-    vae = vx.AutoencoderKLDecoder(vcfg).to(dev).to(elem)
+    vae = (vx.AutoencoderKL if args.init_video else vx.AutoencoderKLDecoder)(vcfg).to(dev).to(elem)
     unet.load_state_dict(synth.unet3d_state_dict(cfg, seed=42, device=dev, dtype=elem, draw_on_device=True))
     unet.release_raw_weights()
     refnet.load_state_dict(synth.refnet_state_dict(cfg, seed=43, device=dev, dtype=elem, draw_on_device=True))
     refnet.release_raw_weights()
     vae.load_state_dict(synth.vae_decoder_state_dict(vcfg, seed=44, device=dev, dtype=elem, draw_on_device=True))
+    if args.init_video:
+        vae.load_state_dict(synth.vae_encoder_state_dict(vcfg, seed=47, device=dev, dtype=elem))
+        vae._prepared_encoder()
     vae._prepared()
     kw = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", clip_sample=False, steps_offset=1,
               prediction_type="v_prediction", rescale_betas_zero_snr=True, timestep_spacing="trailing")
@@ -74,23 +92,44 @@ def main():
     refnet(inp["ref_latents"], timestep=0, encoder_hidden_states=torch.zeros(1, 1, 768, device=dev), return_dict=False)
     reader.update(writer, True)
     sched.set_timesteps(args.steps)
-    timesteps = sched.timesteps.tolist()
+    begin = max(args.steps - min(int(args.steps * args.strength), args.steps), 0)
+    timesteps = sched.timesteps[begin:].tolist()
+    if not timesteps:
+        ap.error("--strength leaves no timestep to run")
     windows = list(uniform(step=0, num_frames=F, context_size=16, context_stride=1, context_overlap=4,
                            closed_loop=False))
     c0 = cfg.block_out_channels[0]
     kps_tokens = ops.ncfhw_to_nhwc(inp["kps_features"], c0).view(2, F, h * h, c0)
     audio = inp["audio_embeddings"].to(elem).contiguous()
 
+    init_video = latent_m = composite = None
+    if args.init_video:
+        init_video = torch.rand(1, 3, F, 8 * h, 8 * h, generator=torch.Generator().manual_seed(7)).to(dev)
+        if args.mask == "lower-half":
+            pixel_m = torch.zeros(F, 8 * h, 8 * h)
+            pixel_m[:, 4 * h:] = 1.0
+            latent_m = latent_mask(pixel_m, F, 8).to(dev)
+            composite = (init_video, pixel_m.reshape(F, -1).to(dev).contiguous())
+    # with the defaults the calls below are the ones this tool has always made (no begin_index, no known)
+    extra = dict(begin_index=begin) if begin or args.init_video else {}
+
     def one_clip(ev=None):
-        lat = inp["latents"] * pipe.scheduler.init_noise_sigma     # (1 but for Euler ancestral)
         if ev:
             ev[0].record()
+        if args.init_video:
+            init = vae.encode_video(init_video)
+            if ev:
+                ev[3].record()
+            lat = torch.empty_like(init)
+            extra["known"] = (init, inp["latents"], latent_m)
+        else:
+            lat = inp["latents"] * pipe.scheduler.init_noise_sigma     # (1 but for Euler ancestral)
         pipe.denoise(lat, kps_tokens, audio, timesteps, windows, 3.5, eta=eta, noise_seed=12345,
                      guidance_rescale=args.guidance_rescale, guidance_start=args.guidance_start,
-                     guidance_end=args.guidance_end)
+                     guidance_end=args.guidance_end, **extra)
         if ev:
             ev[1].record()
-        video = pipe.decode_latents(lat)
+        video = pipe.decode_latents(lat, composite=composite) if composite else pipe.decode_latents(lat)
         if ev:
             ev[2].record()
         return video
@@ -98,7 +137,7 @@ def main():
     for _ in range(args.warmup):
         one_clip()
     torch.cuda.synchronize()
-    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.clips)]
+    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(args.clips)]
     t0 = time.perf_counter()
     for ev in evs:
         video = one_clip(ev)
@@ -107,6 +146,7 @@ def main():
     denoise_ms = sum(e[0].elapsed_time(e[1]) for e in evs) / args.clips
     decode_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / args.clips
     per_clip = [e[0].elapsed_time(e[2]) for e in evs]
+    encode_ms = round(sum(e[0].elapsed_time(e[3]) for e in evs) / args.clips, 2) if args.init_video else None
     assert video.shape == (1, 3, F, 512, 512) and torch.isfinite(video).all()
     # one more clip with events around every update launch (kept out of the timed clips above)
     def update_launch_us(name):
@@ -115,17 +155,21 @@ def main():
         def marked(*a, **k):
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s.record()
-            orig(*a, **k)
+            out = orig(*a, **k)
             e.record()
             marks.append((s, e))
+            return out
         setattr(ops, name, marked)
         try:
             one_clip()
         finally:
             setattr(ops, name, orig)
         torch.cuda.synchronize()
-        return len(marks), 1e3 * sum(s.elapsed_time(e) for s, e in marks) / len(marks)
+        return len(marks), 1e3 * sum(s.elapsed_time(e) for s, e in marks) / max(len(marks), 1)
     n_updates, update_us = update_launch_us(update)
+    blend_launches, blend_us = update_launch_us("known_blend") if args.init_video else (0, None)
+    post = "vae_postprocess_composite" if composite else "vae_postprocess"
+    postprocess_us = round(update_launch_us(post)[1], 2)
     guided = pipe.last_guidance["guided_steps"]
     rescale_us = round(update_launch_us("guidance_rescale")[1], 2) if args.guidance_rescale > 0 and guided else None
     combine_us = round(update_launch_us("combine_units")[1], 2) if rescale_us is None or guided < args.steps else None
@@ -147,7 +191,10 @@ def main():
         frames_per_s=round(F * 1e3 / clip_ms, 3), update_launches=n_updates, update_us=round(update_us, 2),
         ddim_update_us=ddim_us, guidance_rescale=args.guidance_rescale, guidance_start=args.guidance_start,
         guidance_end=args.guidance_end, guided_steps=guided, rescale_us=rescale_us, combine_us=combine_us,
-        clip_ms_min=round(min(per_clip), 2), clip_ms_max=round(max(per_clip), 2), build=vx.lib.lib.vx_build_id().decode())))
+        clip_ms_min=round(min(per_clip), 2), clip_ms_max=round(max(per_clip), 2), init_video=args.init_video,
+        strength=args.strength, mask=args.mask, begin_index=begin, steps_run=len(timesteps), encode_ms=encode_ms,
+        blend_launches=blend_launches, blend_us=None if blend_us is None else round(blend_us, 2), postprocess=post,
+        postprocess_us=postprocess_us, build=vx.lib.lib.vx_build_id().decode())))
 
 
 if __name__ == "__main__":

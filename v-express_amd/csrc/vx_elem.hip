@@ -355,6 +355,38 @@ __global__ void overlap_ancestral_kernel(float* latents, int c, int total_frames
   *lp = out;
 }
 
+// Known-region blend of init-video sampling: latents = m * latents + (1 - m) * (a * init + s * noise), m the latent mask
+// [total_frames, hw] shared by the channels (1 = regenerate, 0 = keep); MASKED = false writes a * init + s * noise (the
+// start latents) and does not read the old value.  One thread per (channel, frame, pixel quad): float4 loads and stores
+// (hw % 4 == 0, 16-byte aligned rows).  The expression keeps this form so that, contracted to fma or not, m = 1 keeps the
+// bits of latents and (m, a, s) = (0, 1, 0) writes the bits of init.
+template <bool MASKED>
+__global__ void known_blend_kernel(float* __restrict__ latents, const float* __restrict__ init,
+                                   const float* __restrict__ noise, const float* __restrict__ mask, int c,
+                                   int total_frames, int hw, float a, float s) {
+  const int hq = hw >> 2;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // (channel, frame, pixel quad)
+  const long per_channel = (long)total_frames * hq;
+  if (idx >= per_channel * c) return;
+  const float4 i4 = reinterpret_cast<const float4*>(init)[idx];
+  const float4 n4 = reinterpret_cast<const float4*>(noise)[idx];
+  float4 k;
+  k.x = a * i4.x + s * n4.x;
+  k.y = a * i4.y + s * n4.y;
+  k.z = a * i4.z + s * n4.z;
+  k.w = a * i4.w + s * n4.w;
+  float4* lp = reinterpret_cast<float4*>(latents) + idx;
+  if (MASKED) {
+    const float4 m = reinterpret_cast<const float4*>(mask)[idx % per_channel];
+    const float4 x = *lp;
+    k.x = m.x * x.x + (1.f - m.x) * k.x;
+    k.y = m.y * x.y + (1.f - m.y) * k.y;
+    k.z = m.z * x.z + (1.f - m.z) * k.z;
+    k.w = m.w * x.w + (1.f - m.w) * k.w;
+  }
+  *lp = k;
+}
+
 // x fp32 [b, c, f, hw] -> out bf16 [(b f), hw, c_pad]; LDS transpose so both sides are coalesced for wide c
 __global__ void ncfhw_to_nhwc_kernel(const float* x, int b, int c, int f, int hw, int c_pad, bf16_t* out) {
   __shared__ float tile[32][33];
@@ -397,6 +429,26 @@ __global__ void vae_post_kernel(const float* x, int ld, int n, int c, int hw, fl
     float v = src[ch] * 0.5f + 0.5f;
     v = fminf(fmaxf(v, 0.f), 1.f);
     out[((size_t)fr * c + ch) * hw + px] = v;
+  }
+}
+
+// vae_post_kernel composited onto the init video in the same pass: out = M * v + (1 - M) * init, M the pixel mask of the
+// frame (mask_stride = 0: one mask for every frame), read once per pixel and shared by the channels; init is laid out
+// [c, total_frames, hw].  Same thread mapping as vae_post_kernel: the writes (and the init / mask reads) are coalesced.
+__global__ void vae_post_composite_kernel(const float* __restrict__ x, int ld, int n, int c, int hw,
+                                          const float* __restrict__ init, int total_frames, int frame0,
+                                          const float* __restrict__ mask, long mask_stride, float* __restrict__ out) {
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // (n, px)
+  if (idx >= (long)n * hw) return;
+  int px = (int)(idx % hw);
+  int fr = (int)(idx / hw);
+  const float* src = x + idx * ld;
+  const float m = mask[(size_t)(frame0 + fr) * mask_stride + px];
+  for (int ch = 0; ch < c; ++ch) {
+    float v = src[ch] * 0.5f + 0.5f;
+    v = fminf(fmaxf(v, 0.f), 1.f);
+    const float keep = init[((size_t)ch * total_frames + frame0 + fr) * hw + px];
+    out[((size_t)fr * c + ch) * hw + px] = m * v + (1.f - m) * keep;
   }
 }
 
@@ -613,6 +665,24 @@ extern "C" int vx_overlap_ancestral_step(float* latents, int c, int total_frames
   return vx_check_launch("vx_overlap_ancestral_step");
 }
 
+extern "C" int vx_known_blend(float* latents, const float* init, const float* noise, const float* mask, int c,
+                              int total_frames, int hw, float a, float s, void* stream) {
+  VX_REQUIRE(latents && init && noise && c > 0 && total_frames > 0 && hw > 0 && (hw % 4) == 0 &&
+                 ((uintptr_t)latents % 16) == 0 && ((uintptr_t)init % 16) == 0 && ((uintptr_t)noise % 16) == 0 &&
+                 ((uintptr_t)mask % 16) == 0,
+             "vx_known_blend: bad arguments (hw %% 4 == 0 and 16-byte aligned latents / init / noise / mask required)");
+  VX_REQUIRE(a >= 0.f && s >= 0.f, "vx_known_blend: the signal / noise pair (a, s) must not be negative");
+  const long quads = (long)c * total_frames * (hw / 4);
+  VX_REQUIRE(quads <= 0x7fffffffL * 256L, "vx_known_blend: too many elements for one launch");
+  if (mask)
+    hipLaunchKernelGGL(known_blend_kernel<true>, grid1d(quads), dim3(256), 0, (hipStream_t)stream, latents, init, noise,
+                       mask, c, total_frames, hw, a, s);
+  else
+    hipLaunchKernelGGL(known_blend_kernel<false>, grid1d(quads), dim3(256), 0, (hipStream_t)stream, latents, init,
+                       noise, mask, c, total_frames, hw, a, s);
+  return vx_check_launch("vx_known_blend");
+}
+
 extern "C" int vx_ncfhw_to_nhwc(const float* x, int b, int c, int f, int hw, int c_pad, void* out, void* stream) {
   VX_REQUIRE(x && out && c_pad >= c && (long)b * f <= 65535, "vx_ncfhw_to_nhwc: bad arguments");
   dim3 grid((hw + 31) / 32, (c_pad + 31) / 32, b * f);
@@ -632,6 +702,20 @@ extern "C" int vx_vae_postprocess(const float* x, int ld, int n, int c, int hw, 
   VX_REQUIRE(x && out && ld >= c, "vx_vae_postprocess: bad arguments");
   hipLaunchKernelGGL(vae_post_kernel, grid1d((long)n * hw), dim3(256), 0, (hipStream_t)stream, x, ld, n, c, hw, out);
   return vx_check_launch("vx_vae_postprocess");
+}
+
+extern "C" int vx_vae_postprocess_composite(const float* x, int ld, int n, int c, int hw, const float* init,
+                                            int total_frames, int frame0, const float* mask, int mask_frames,
+                                            float* out, void* stream) {
+  VX_REQUIRE(x && out && init && mask && ld >= c && n > 0 && c > 0 && hw > 0,
+             "vx_vae_postprocess_composite: bad arguments");
+  VX_REQUIRE(frame0 >= 0 && total_frames > 0 && n <= total_frames - frame0,
+             "vx_vae_postprocess_composite: frames frame0 .. frame0 + n - 1 must lie inside the init video");
+  VX_REQUIRE(mask_frames == 1 || mask_frames == total_frames,
+             "vx_vae_postprocess_composite: the mask has one frame or one per frame of the init video");
+  hipLaunchKernelGGL(vae_post_composite_kernel, grid1d((long)n * hw), dim3(256), 0, (hipStream_t)stream, x, ld, n, c,
+                     hw, init, total_frames, frame0, mask, mask_frames == 1 ? 0L : (long)hw, out);
+  return vx_check_launch("vx_vae_postprocess_composite");
 }
 
 extern "C" int vx_median3d(const float* video, int c, int f, int h, int w, float* out_f32, void* out_u8, void* stream) {

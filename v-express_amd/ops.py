@@ -1400,6 +1400,31 @@ def overlap_ancestral_step(latents, preds, terms, frame_ids, counts, coef, seed,
                                            _stream()), "vx_overlap_ancestral_step")
 
 
+def known_blend(latents, init, noise, mask, a, s):
+    """Known-region blend of init-video sampling, in place: latents fp32 [1,C,F,h,w] <- m * latents + (1 - m) *
+    (a * init + s * noise); init / noise fp32 shaped like latents, mask fp32 [F, h*w] in [0, 1] (1 = regenerate) shared
+    by the channels, (a, s) >= 0 the scheduler's noise_coefficients of the level the latents are at.  mask None writes
+    a * init + s * noise (the start latents)."""
+    b, c, F, h, w = latents.shape
+    for t, name in ((latents, "latents"), (init, "init"), (noise, "noise")):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError(f"known_blend: contiguous float32 {name} expected")
+    if b != 1 or init.shape != latents.shape or noise.shape != latents.shape:
+        raise ValueError("known_blend: latents / init / noise must share one [1, C, F, h, w] shape")
+    if (h * w) % 4:
+        raise ValueError("known_blend: h * w % 4 == 0 required")
+    if mask is not None:
+        if mask.dtype != torch.float32 or not mask.is_contiguous():
+            raise TypeError("known_blend: contiguous float32 mask expected")
+        if tuple(mask.shape) != (F, h * w):
+            raise ValueError(f"known_blend: the mask must be [F, h * w] = [{F}, {h * w}], got {tuple(mask.shape)}")
+    a, s = float(a), float(s)
+    if not (a >= 0.0 and s >= 0.0):
+        raise ValueError(f"known_blend: the signal / noise pair must not be negative, got ({a}, {s})")
+    L.check(_lib.vx_known_blend(_ptr(latents), _ptr(init), _ptr(noise), _ptr(mask), c, F, h * w, a, s, _stream()),
+            "vx_known_blend")
+
+
 def ncfhw_to_nhwc(x, c_pad=None):
     """fp32 [b, C, f, h, w] -> bf16 [(b f), h*w, c_pad]."""
     b, c, f, h, w = x.shape
@@ -1446,4 +1471,30 @@ def vae_postprocess(x, n, c, h, w):
     """fp32 [n*hw, ld] -> fp32 [n, c, h, w] = clamp(x/2 + 0.5, 0, 1)."""
     out = torch.empty((n, c, h, w), device=x.device, dtype=torch.float32)
     L.check(_lib.vx_vae_postprocess(_ptr(x), x.stride(0), n, c, h * w, _ptr(out), _stream()), "vx_vae_postprocess")
+    return out
+
+
+def vae_postprocess_composite(x, n, c, h, w, init_video, mask, frame0=0):
+    """`vae_postprocess` composited onto the init video in the same pass: fp32 [n*hw, ld] -> fp32 [n, c, h, w] =
+    M * clamp(x/2 + 0.5, 0, 1) + (1 - M) * init_video[:, :, frame0 + i]; init_video fp32 [1, c, F, h, w] in [0, 1],
+    mask fp32 [F or 1, h*w] in [0, 1] at pixel resolution (1 = take the decoded pixel)."""
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or x.shape[0] != n * h * w or x.stride(0) < c:
+        raise TypeError("vae_postprocess_composite: float32 rows [n * h * w, ld >= c] expected")
+    for t, name in ((init_video, "init video"), (mask, "mask")):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError(f"vae_postprocess_composite: contiguous float32 {name} expected")
+    if init_video.dim() != 5 or init_video.shape[0] != 1 or init_video.shape[1] != c or init_video.shape[3:] != (h, w):
+        raise ValueError(f"vae_postprocess_composite: the init video must be [1, {c}, F, {h}, {w}], got "
+                         f"{tuple(init_video.shape)}")
+    F = init_video.shape[2]
+    if mask.dim() != 2 or mask.shape[1] != h * w or mask.shape[0] not in (1, F):
+        raise ValueError(f"vae_postprocess_composite: the mask must be [{F} or 1, {h * w}], got {tuple(mask.shape)}")
+    frame0 = int(frame0)
+    if n < 1 or frame0 < 0 or frame0 + n > F:
+        raise ValueError(f"vae_postprocess_composite: frames {frame0} .. {frame0 + n - 1} lie outside the {F} frames "
+                         f"of the init video")
+    out = torch.empty((n, c, h, w), device=x.device, dtype=torch.float32)
+    L.check(_lib.vx_vae_postprocess_composite(_ptr(x), x.stride(0), n, c, h * w, _ptr(init_video), F, frame0,
+                                              _ptr(mask), mask.shape[0], _ptr(out), _stream()),
+            "vx_vae_postprocess_composite")
     return out

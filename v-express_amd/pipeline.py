@@ -72,6 +72,50 @@ def check_guidance(guidance_rescale, guidance_start, guidance_end, n):
     return phi, guided_steps(n, start, end)
 
 
+def check_init(init_video, init_latents, mask, video_length, height, width, scale, channels=4):
+    """Validates the init-video arguments of __call__ against the clip's geometry (ValueError); returns the mask at pixel
+    resolution as float32 [F or 1, H, W] on its own device, or None."""
+    if init_video is not None and init_latents is not None:
+        raise ValueError("init_video and init_latents are two forms of one input: pass one of them")
+    if mask is not None and init_video is None and init_latents is None:
+        raise ValueError("mask says which part of an init clip to keep: pass init_video or init_latents with it")
+    F, H, W = int(video_length), int(height), int(width)
+    if init_video is not None:
+        if not isinstance(init_video, torch.Tensor) or tuple(init_video.shape) != (1, 3, F, H, W):
+            raise ValueError(f"init_video must be a [1, 3, {F}, {H}, {W}] tensor (video_length, height, width), got "
+                             f"{tuple(getattr(init_video, 'shape', ()))}")
+        lo, hi = float(init_video.min()), float(init_video.max())
+        if not (lo >= 0.0 and hi <= 1.0):
+            raise ValueError(f"init_video values must lie in [0, 1], got [{lo}, {hi}]")
+    if init_latents is not None:
+        want = (1, channels, F, H // scale, W // scale)
+        if not isinstance(init_latents, torch.Tensor) or tuple(init_latents.shape) != want:
+            raise ValueError(f"init_latents must be a {list(want)} tensor (video_length, height / {scale}, width / "
+                             f"{scale}), got {tuple(getattr(init_latents, 'shape', ()))}")
+    if mask is None:
+        return None
+    if not isinstance(mask, torch.Tensor) or mask.dim() not in (3, 4) or (mask.dim() == 4 and mask.shape[1] != 1):
+        raise ValueError(f"mask must be [F or 1, 1, H, W] or [F or 1, H, W], got {tuple(getattr(mask, 'shape', ()))}")
+    m = mask[:, 0] if mask.dim() == 4 else mask
+    if m.shape[0] not in (1, F) or tuple(m.shape[1:]) != (H, W):
+        raise ValueError(f"mask must have {F} frames or 1, of {H} x {W} pixels (video_length, height, width), got "
+                         f"{tuple(mask.shape)}")
+    if not (m.dtype == torch.bool or m.is_floating_point()):
+        raise ValueError(f"mask must be a float or bool tensor, got {m.dtype}")
+    m = m.to(torch.float32)
+    lo, hi = float(m.min()), float(m.max())
+    if not (lo >= 0.0 and hi <= 1.0):
+        raise ValueError(f"mask values must lie in [0, 1], got [{lo}, {hi}]")
+    return m
+
+
+def latent_mask(pixel_mask, video_length, scale):
+    """The latent mask of a pixel mask (float32 [F or 1, H, W]): the scale x scale box mean, one row per frame,
+    float32 [F, (H / scale) * (W / scale)].  A hard pixel edge inside a latent cell becomes a soft latent edge."""
+    m = torch.nn.functional.avg_pool2d(pixel_mask[:, None].cpu(), scale)[:, 0]
+    return m.expand(video_length, -1, -1).reshape(video_length, -1).contiguous()
+
+
 class VExpressPipeline:
     def __init__(self, vae, reference_net, denoising_unet, v_kps_guider=None, audio_processor=None,
                  audio_encoder=None, audio_projection=None, scheduler=None, image_proj_model=None, tokenizer=None,
@@ -98,6 +142,10 @@ class VExpressPipeline:
         # the guidance controls of the last denoise() call: dict(guided_steps, steps, rescale, unguided_schedule), the
         # last one the last_schedule-style dict of the conditional-only plan of its unguided steps, or None
         self.last_guidance = {}
+        # init-video sampling of the last denoise() call: dict(begin_index, masked, blend_launches) - the step index the
+        # loop started at, whether a latent mask was blended in after every step, and the vx_known_blend launches of the
+        # call (the one that forms the start latents included; 0 without an init clip)
+        self.last_init = {}
         # batch rows per UNet call: 2 = the two CFG halves of one window; 4 (default), 6, ... also merge consecutive
         # windows of this rank into one call.  Every kernel is batch-invariant, so the rows come out bit-identical;
         # merged calls measure 4-5 % faster (profiles/r02e_host_overhead.json: b = 3 74.0 ms vs 49.2 + 28.2 ms,
@@ -210,9 +258,14 @@ class VExpressPipeline:
             raise ValueError(
                 f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
                 f" size of {batch_size}. Make sure the batch size matches the length of the generators.")
+        return self._initial_noise(shape, device, generator, latents) * self.scheduler.init_noise_sigma
+
+    @staticmethod
+    def _initial_noise(shape, device, generator, latents=None):
+        """The N(0,1) draw of prepare_latents (or the caller's `latents`) before init_noise_sigma: float32 on `device`."""
         if latents is None:
             latents = torch.randn(shape, generator=generator, device="cpu", dtype=torch.float32)
-        return latents.to(device=device, dtype=torch.float32) * self.scheduler.init_noise_sigma
+        return latents.to(device=device, dtype=torch.float32)
 
     # ------------------------------------------------------------------ the hot loop
     def _sampler(self, eta=0.0):
@@ -335,7 +388,7 @@ class VExpressPipeline:
     @_in_unet_element_type
     def denoise(self, latents, kps_tokens, audio, timesteps, windows, guidance_scale, callback=None,
                 callback_steps=1, *, begin_index=None, eta=0.0, noise_seed=None, guidance_rescale=0.0,
-                guidance_start=0.0, guidance_end=1.0):
+                guidance_start=0.0, guidance_end=1.0, known=None):
         """pipelines/v_express_pipeline.py:526-583.  latents fp32 [1,4,F,h,w] (device, updated in place);
         kps_tokens bf16 [b, F, hw, C0]; audio bf16 [b, F, n_ctx, 768] with b = 2 (uncond, cond) under classifier-free
         guidance (guidance_scale > 1, :443) and b = 1 (the conditional row only) without.
@@ -347,10 +400,28 @@ class VExpressPipeline:
         Guidance controls (classifier-free guidance only; every sampler): step i of the N timesteps is guided iff
         i / N >= guidance_start and (i + 1) / N <= guidance_end, any other step computes the conditional rows only and
         takes them as the prediction; guidance_rescale = phi > 0 scales each window's guided prediction g by
-        1 + phi (std(cond) / std(g) - 1) before the overlap sum (diffusers' rescale_noise_cfg, vx_guidance_rescale)."""
+        1 + phi (std(cond) / std(g) - 1) before the overlap sum (diffusers' rescale_noise_cfg, vx_guidance_rescale).
+        Init-video sampling (every sampler): known = (init, noise, m) - the clip's clean latents and the N(0,1) tensor,
+        fp32 shaped like `latents`, and the latent mask fp32 [F, h*w] in [0, 1] (1 = regenerate, 0 = keep) or None.  The
+        loop then starts from a_b init + s_b noise, b = begin_index (what `latents` held is not read), with (a_j, s_j)
+        the scheduler's noise_coefficients(j); with a mask, after the update of step index i the kept part is put back
+        at the level the latents now have, x = m x + (1 - m)(a_{i+1} init + s_{i+1} noise), and after the last of
+        `timesteps` it is init itself, (a, s) = (1, 0), as in diffusers' inpaint loop (vx_known_blend; the same noise
+        at every step; the multistep history and the ancestral noise are left alone; a callback sees the blended
+        latents).  m = None is plain img2img: no launch after the start."""
         kind = self._sampler(eta)
         guidance_rescale, guided = check_guidance(guidance_rescale, guidance_start, guidance_end, len(timesteps))
-        if kind != "ddim":
+        init = noise = kmask = None
+        if known is not None:
+            init, noise, kmask = known
+            for t, name in ((init, "init"), (noise, "noise")):
+                if tuple(t.shape) != tuple(latents.shape):
+                    raise ValueError(f"known: {name} must be shaped like the latents {tuple(latents.shape)}, got "
+                                     f"{tuple(t.shape)}")
+            want = (latents.shape[2], latents.shape[3] * latents.shape[4])
+            if kmask is not None and tuple(kmask.shape) != want:
+                raise ValueError(f"known: the latent mask must be [F, h * w] = {list(want)}, got {tuple(kmask.shape)}")
+        if kind != "ddim" or known is not None:
             all_ts = [int(t) for t in self.scheduler.timesteps.tolist()]
             if begin_index is None:
                 begin_index = len(all_ts) - len(timesteps)
@@ -410,7 +481,18 @@ class VExpressPipeline:
             coefs = self._ancestral_coefficients(kind, timesteps, begin_index, eta)
             noise_seed = int(noise_seed)
         euler_a = kind == "euler-a"
-        if euler_a and timesteps:
+        # init-video sampling: the (a, s) of the start and of the blend after every step, resolved on the host
+        blend = None
+        if kmask is not None:
+            blend = [(1.0, 0.0) if i == len(timesteps) - 1 else self.scheduler.noise_coefficients(begin_index + i + 1)
+                     for i in range(len(timesteps))]
+        self.last_init = dict(begin_index=begin_index, masked=kmask is not None,
+                              blend_launches=0 if known is None else 1 + (len(timesteps) if blend else 0))
+        if known is not None:
+            # the start latents, in the frame the loop runs in (Euler ancestral: the VP frame, (init + sigma noise) /
+            # sqrt(1 + sigma^2))
+            ops.known_blend(latents, init, noise, None, *self.scheduler.noise_coefficients(begin_index))
+        elif euler_a and timesteps:
             latents.mul_(1.0 / self.scheduler.frame_scale(begin_index))          # VE -> VP, once
         for i, t in enumerate(timesteps):
             t = int(t)
@@ -438,6 +520,9 @@ class VExpressPipeline:
                                            begin_index + i)
             else:
                 ops.overlap_ddim_step(latents, preds, terms, frame_ids, counts, self.scheduler.step_coefficients(t))
+            if blend is not None:
+                # the kept part again, at the level the latents have now (init itself after the last step)
+                ops.known_blend(latents, init, noise, kmask, *blend[i])
             if callback is not None and i % callback_steps == 0:
                 # Euler ancestral: the callback sees the scheduler's own (VE) frame, as the reference's does
                 callback(i, t, latents * self.scheduler.frame_scale(begin_index + i + 1) if euler_a else latents)
@@ -449,16 +534,21 @@ class VExpressPipeline:
 
     @torch.no_grad()
     @_in_unet_element_type
-    def decode_latents(self, latents, chunk=8):
-        """pipelines/v_express_pipeline.py:152-166; frames are split evenly over the ranks when distributed."""
+    def decode_latents(self, latents, chunk=8, composite=None):
+        """pipelines/v_express_pipeline.py:152-166; frames are split evenly over the ranks when distributed.
+        composite = (init_video fp32 [1, 3, F, H, W], pixel mask fp32 [F or 1, H * W]), both on the device: the video is
+        mask * decoded + (1 - mask) * init_video, formed inside the post-process launch."""
         dc = self.dist
         F = latents.shape[2]
+        comp = {} if composite is None else dict(init_video=composite[0], mask=composite[1])
         if not dc.enabled:
-            return self.vae.decode_video(latents, chunk=chunk)
+            return self.vae.decode_video(latents, chunk=chunk, **comp)
         spans = split_frames(F, dc.world_size)
         lo, hi = spans[dc.rank]
         per = spans[0][1] - spans[0][0]
-        part = self.vae.decode_video(latents[:, :, lo:hi].contiguous(), chunk=chunk) if hi > lo else None
+        if comp:
+            comp["frame0"] = lo
+        part = self.vae.decode_video(latents[:, :, lo:hi].contiguous(), chunk=chunk, **comp) if hi > lo else None
         Hh, Ww = latents.shape[-2] * self.vae_scale_factor, latents.shape[-1] * self.vae_scale_factor
         buf = torch.zeros((per, 3, Hh, Ww), device=latents.device, dtype=torch.float32)
         if part is not None:
@@ -479,11 +569,25 @@ class VExpressPipeline:
                  num_pad_audio_frames=2, do_multi_devices_inference=False, save_gpu_memory=False,
                  reference_latents=None, kps_features=None, audio_embeddings=None, latents=None,
                  noise_seed: Optional[int] = None, output_device="cpu", decode=True, guidance_rescale: float = 0.0,
-                 guidance_start: float = 0.0, guidance_end: float = 1.0, **kwargs):
-        # an unsupported scheduler, eta with one other than DDIM, or guidance controls out of range fail here, before
-        # the prologue
+                 guidance_start: float = 0.0, guidance_end: float = 1.0, init_video=None, init_latents=None,
+                 mask=None, composite=True, **kwargs):
+        """Init-video sampling (diffusers' img2img / inpaint semantics for a 4-channel UNet): `init_video` fp32
+        [1, 3, F, H, W] in [0, 1] (VAE-encoded here; needs v_express_amd.AutoencoderKL) or `init_latents`
+        [1, 4, F, h, w] (clean, already scaled) makes the loop start from the clip noised to the level of `strength`
+        instead of from pure noise; `mask` ([F or 1, 1, H, W] or [F or 1, H, W], float or bool in [0, 1]; 1 =
+        regenerate, 0 = keep) restricts the change to a region (its 8 x 8 box mean is the latent mask), and with
+        `init_video` and `composite` the kept pixels of the output are the caller's own, not their VAE round trip.
+        `latents` / `generator` give the N(0,1) noise, as without an init clip."""
+        # an unsupported scheduler, eta with one other than DDIM, guidance controls out of range or init-video arguments
+        # that do not fit the clip fail here, before the prologue
         kind = self._sampler(eta)
         check_guidance(guidance_rescale, guidance_start, guidance_end, max(int(num_inference_steps), 1))
+        pixel_mask = check_init(init_video, init_latents, mask, video_length, height, width, self.vae_scale_factor,
+                                self.denoising_unet.in_channels)
+        if init_video is not None and not hasattr(self.vae, "encode_video"):
+            raise NotImplementedError("this VAE has no encoder half (AutoencoderKLDecoder): construct "
+                                      "v_express_amd.AutoencoderKL and load encoder.* / quant_conv.*, or pass "
+                                      "init_latents=[1,4,F,h/8,w/8] (already scaled by 0.18215)")
         dev = self.device
         do_cfg = guidance_scale > 1.0
         # timesteps (retrieve_timesteps + get_timesteps, :448-449)
@@ -517,12 +621,31 @@ class VExpressPipeline:
         ehs0 = torch.zeros((1, 1, self.denoising_unet.cfg.cross_attention_dim), dtype=torch.float32, device=dev)
         self.reference_net(reference_latents.to(dev), timestep=0, encoder_hidden_states=ehs0, return_dict=False)
         reader.update(writer, do_cfg, dtype=self.dtype)
-        lat = self.prepare_latents(num_images_per_prompt, self.denoising_unet.in_channels, width, height,
-                                   video_length, self.dtype, dev, generator, latents)
-        if self.dist.enabled and latents is None:
-            # every rank drew from its own CPU generator; the loop needs identical step-start latents on all ranks
-            # (each rank's UNet inputs are gathered from them and every rank applies the DDIM update): rank 0's draw wins
-            lat = self.dist.broadcast(lat.contiguous(), src=0)
+        known = video_dev = None
+        if init_video is None and init_latents is None:
+            lat = self.prepare_latents(num_images_per_prompt, self.denoising_unet.in_channels, width, height,
+                                       video_length, self.dtype, dev, generator, latents)
+            if self.dist.enabled and latents is None:
+                # every rank drew from its own CPU generator; the loop needs identical step-start latents on all ranks
+                # (each rank's UNet inputs are gathered from them and every rank applies the DDIM update): rank 0's
+                # draw wins
+                lat = self.dist.broadcast(lat.contiguous(), src=0)
+        else:
+            # the same draw, kept as N(0,1): the loop forms the start latents from it and reuses it at every blend.
+            # Rank 0's noise wins as its latents do; every rank encodes the init video itself (batch-invariant kernels)
+            h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
+            noise = self._initial_noise((1, self.denoising_unet.in_channels, video_length, h, w), dev, generator,
+                                        latents).contiguous()
+            if self.dist.enabled and latents is None:
+                noise = self.dist.broadcast(noise, src=0)
+            if init_video is not None:
+                video_dev = init_video.to(device=dev, dtype=torch.float32).contiguous()
+                init = self.vae.encode_video(video_dev)
+            else:
+                init = init_latents.to(device=dev, dtype=torch.float32).contiguous()
+            m = None if pixel_mask is None else latent_mask(pixel_mask, video_length, self.vae_scale_factor).to(dev)
+            known = (init, noise, m)
+            lat = torch.empty_like(noise)
         if kind in ("ddim-eta", "euler-a") and noise_seed is None:
             # the ancestral noise is drawn on the device from one 64-bit seed, taken from the generator AFTER the
             # initial latents (which so stay what they are for a given generator); rank 0's seed wins, like its latents
@@ -541,14 +664,18 @@ class VExpressPipeline:
             ev[0].record()
         self.denoise(lat, kps_tokens, audio, timesteps, windows, guidance_scale, callback, callback_steps or 1,
                      begin_index=begin_index, eta=eta, noise_seed=noise_seed, guidance_rescale=guidance_rescale,
-                     guidance_start=guidance_start, guidance_end=guidance_end)
+                     guidance_start=guidance_start, guidance_end=guidance_end, known=known)
         if timed:
             ev[1].record()
         reader.clear()
         writer.clear()
         if not decode:
             return lat
-        video = self.decode_latents(lat)
+        comp = None
+        if composite and video_dev is not None and pixel_mask is not None:
+            # the kept pixels are the caller's own: a VAE round trip must not degrade them
+            comp = (video_dev, pixel_mask.reshape(pixel_mask.shape[0], -1).to(dev).contiguous())
+        video = self.decode_latents(lat, composite=comp)
         if timed:
             ev[2].record()
         self._events = ev

@@ -35,6 +35,20 @@ def _betas(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_bet
     return betas
 
 
+def _per_sample(v, sample):
+    """A per-timestep coefficient list as a tensor of `sample`'s dtype that broadcasts over its batch axis."""
+    t = torch.tensor(v, dtype=torch.float64).to(device=sample.device, dtype=sample.dtype).flatten()
+    return t.reshape((-1,) + (1,) * (sample.dim() - 1)) if t.numel() > 1 else t.reshape(())
+
+
+def _timestep_list(timesteps):
+    if isinstance(timesteps, torch.Tensor):
+        return [float(t) for t in timesteps.flatten().tolist()]
+    if isinstance(timesteps, (list, tuple)):
+        return [float(t) for t in timesteps]
+    return [float(timesteps)]
+
+
 class DDIMScheduler:
     order = 1
 
@@ -104,6 +118,24 @@ class DDIMScheduler:
         sig, k = eta * math.sqrt(var), math.sqrt(max(kk, 0.0))
         sa, s1a = math.sqrt(a), math.sqrt(1.0 - a)
         return sa, s1a, k / s1a, -(math.sqrt(ap) - k * sa / s1a), sig
+
+    def noise_coefficients(self, j):
+        """(a_j, s_j) = (sqrt(abar), sqrt(1 - abar)) of timesteps[j], the level the latents have at step index j;
+        j = len(timesteps): the level after the last step (final_alpha_cumprod).  Float64 arithmetic on the float32
+        table: x_j = a_j x0 + s_j noise is `add_noise(x0, noise, timesteps[j])`."""
+        n = len(self.timesteps)
+        if not 0 <= j <= n:
+            raise IndexError(f"step index {j} outside [0, {n}]")
+        abar = float(self.alphas_cumprod[int(self.timesteps[j])]) if j < n else float(self.final_alpha_cumprod)
+        return math.sqrt(abar), math.sqrt(1.0 - abar)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' DDIMScheduler.add_noise: sqrt(abar_t) x0 + sqrt(1 - abar_t) noise, t one timestep or one per
+        sample of the batch (host torch arithmetic; the loop forms its start latents with vx_known_blend)."""
+        abar = [float(self.alphas_cumprod[int(t)]) for t in _timestep_list(timesteps)]
+        a = _per_sample([math.sqrt(v) for v in abar], original_samples)
+        s = _per_sample([math.sqrt(1.0 - v) for v in abar], original_samples)
+        return a * original_samples + s * noise
 
     def step(self, model_output, timestep, sample, eta=0.0, **unused):
         if eta != 0.0:
@@ -228,6 +260,35 @@ class DPMSolverMultistepScheduler:
             r = (math.log(sg[i - 1]) - math.log(s0)) / h
             B = 0.5 * A / r
         return a_i, sd_i, c_x, A + B, B
+
+    def _indices_of(self, timesteps):
+        """Step indices of schedule timesteps (diffusers' index_for_timestep: the first match)."""
+        own = [float(t) for t in self.timesteps.tolist()]
+        out = []
+        for t in _timestep_list(timesteps):
+            if t not in own:
+                raise ValueError(f"timestep {t} is not in this schedule")
+            out.append(own.index(t))
+        return out
+
+    def noise_coefficients(self, j):
+        """(a_j, s_j) = (alpha_t, sigma_t) of sigmas[j], the level the latents have at step index j (j = number of
+        steps: the final sigma).  Float64 arithmetic on the float32 sigmas."""
+        if self.sigmas is None or self.num_inference_steps is None:
+            raise RuntimeError("call set_timesteps() first")
+        if not 0 <= j <= self.num_inference_steps:
+            raise IndexError(f"step index {j} outside [0, {self.num_inference_steps}]")
+        sg = float(self.sigmas[j])
+        a = 1.0 / math.sqrt(sg * sg + 1.0)
+        return a, sg * a
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' DPMSolverMultistepScheduler.add_noise: alpha_t x0 + sigma_t noise at the schedule's own timesteps
+        (one, or one per sample of the batch)."""
+        pairs = [self.noise_coefficients(i) for i in self._indices_of(timesteps)]
+        a = _per_sample([p[0] for p in pairs], original_samples)
+        s = _per_sample([p[1] for p in pairs], original_samples)
+        return a * original_samples + s * noise
 
     def step(self, model_output, timestep, sample, return_dict=True, **unused):
         """One update on tensors (v-prediction `model_output`), keeping the step index and the last x0 like diffusers."""
@@ -358,6 +419,29 @@ class EulerAncestralDiscreteScheduler:
         s_down = math.sqrt(s1 * s1 - s_up * s_up)
         r1 = math.sqrt(1.0 + s1 * s1)
         return alpha_s, sigma_s, r * s_down / (s * r1), -(1.0 - s_down / s) / r1, s_up / r1
+
+    def noise_coefficients(self, j):
+        """(a_j, s_j) = (1, sigma_j) / sqrt(1 + sigma_j^2) of sigmas[j]: the variance-preserving pair of the frame the
+        loop runs in (x_vp = x_ve / sqrt(1 + sigma^2)); j = number of steps: the final sigma = 0, (1, 0)."""
+        n = self.num_inference_steps
+        if n is None:
+            raise RuntimeError("call set_timesteps() first")
+        if not 0 <= j <= n:
+            raise IndexError(f"step index {j} outside [0, {n}]")
+        sg = float(self.sigmas[j])
+        a = 1.0 / math.sqrt(sg * sg + 1.0)
+        return a, sg * a
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' EulerAncestralDiscreteScheduler.add_noise, in the scheduler's own (VE) frame: x0 + sigma noise at
+        the schedule's own timesteps (one, or one per sample of the batch)."""
+        own = [float(t) for t in self.timesteps.tolist()]
+        sig = []
+        for t in _timestep_list(timesteps):
+            if t not in own:
+                raise ValueError(f"timestep {t} is not in this schedule")
+            sig.append(float(self.sigmas[own.index(t)]))
+        return original_samples + _per_sample(sig, original_samples) * noise
 
     def frame_scale(self, i):
         """sqrt(1 + sigmas[i]^2): x_ve = frame_scale(i) x_vp at step index i (1 at the final sigma = 0)."""

@@ -109,10 +109,17 @@ class AutoencoderKLDecoder(DeviceModule):
         img = ops.nhwc_to_ncfhw(out, n, self.cfg.out_channels, 1, H, W)[:, :, 0]
         return SimpleNamespace(sample=img)
 
-    def decode_video(self, latents, chunk=8):
+    def decode_video(self, latents, chunk=8, init_video=None, mask=None, frame0=0):
         """VExpressPipeline.decode_latents (pipelines/v_express_pipeline.py:152-166) on device:
-        latents fp32 [1, 4, F, h, w] -> video fp32 [1, 3, F, 8h, 8w] in [0, 1]."""
+        latents fp32 [1, 4, F, h, w] -> video fp32 [1, 3, F, 8h, 8w] in [0, 1].
+        With `init_video` (fp32 [1, 3, F_clip, 8h, 8w] in [0, 1], device) and `mask` (fp32 [F_clip or 1, 8h * 8w] in
+        [0, 1]) the post-process composites in the same pass: mask * decoded + (1 - mask) * init_video, the latents
+        being frames frame0 .. frame0 + F - 1 of the clip (vx_vae_postprocess_composite)."""
         b, c, F, h, w = latents.shape
+        if (init_video is None) != (mask is None):
+            raise ValueError("decode_video: init_video and mask come together")
+        if init_video is not None and b != 1:
+            raise ValueError("decode_video: the composite takes one clip (batch 1)")
         lat = (latents.float() / self.cfg.scaling_factor)
         frames = []
         for f0 in range(0, F, chunk):
@@ -120,7 +127,11 @@ class AutoencoderKLDecoder(DeviceModule):
             n = part.shape[2] * b
             zt = ops.ncfhw_to_nhwc(part.contiguous(), 8)
             out, H, W = self.decode_tokens(zt, n, h, w)
-            frames.append(ops.vae_postprocess(out, n, self.cfg.out_channels, H, W))
+            if init_video is None:
+                frames.append(ops.vae_postprocess(out, n, self.cfg.out_channels, H, W))
+            else:
+                frames.append(ops.vae_postprocess_composite(out, n, self.cfg.out_channels, H, W, init_video, mask,
+                                                            frame0 + f0))
         video = torch.cat(frames)                                    # [(b F), 3, H, W]
         return video.view(b, F, self.cfg.out_channels, video.shape[-2], video.shape[-1]).permute(0, 2, 1, 3, 4)
 
@@ -189,3 +200,19 @@ class AutoencoderKL(AutoencoderKLDecoder):
         m = ops.gemm(m, P.quant.w, P.quant.b, out_f32=True)                     # [n*hw, 8] fp32: mean | logvar
         mean = ops.nhwc_to_ncfhw(m, n, cfg.latent_channels, 1, H, W)[:, :, 0]
         return SimpleNamespace(latent_dist=SimpleNamespace(mean=mean))
+
+    def encode_video(self, video, chunk=8):
+        """video [1, 3, F, H, W] in [0, 1] (any float dtype / device) -> clean latents fp32 [1, 4, F, H/8, W/8] on the
+        device: posterior mean of 2 * video - 1 times the scaling factor, the transform
+        VExpressPipeline.prepare_reference_latent applies to the reference image.  `chunk` frames per encoder call, like
+        decode_video (the kernels are batch-invariant: the chunk size does not change a bit)."""
+        if video.dim() != 5 or video.shape[0] != 1 or video.shape[1] != self.cfg.out_channels:
+            raise ValueError(f"encode_video: [1, {self.cfg.out_channels}, F, H, W] expected, got {tuple(video.shape)}")
+        if int(chunk) < 1:
+            raise ValueError(f"encode_video: chunk must be >= 1, got {chunk}")
+        x = video[0].to(self._device).float().permute(1, 0, 2, 3)              # [F, 3, H, W]
+        parts = []
+        for f0 in range(0, x.shape[0], int(chunk)):
+            mean = self.encode(2.0 * x[f0:f0 + int(chunk)] - 1.0).latent_dist.mean
+            parts.append(mean * self.cfg.scaling_factor)
+        return torch.cat(parts).permute(1, 0, 2, 3).unsqueeze(0).contiguous()
