@@ -431,6 +431,22 @@ int64_t vx_guidance_rescale_ws_floats(int n_windows, int f, int hw);
 int vx_guidance_rescale(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c, int f,
                         int hw, float guidance, float phi, float* workspace, int64_t ws_floats, float* preds,
                         void* stream);
+/* Three-row guidance with a separate audio scale (`audio_guidance_scale`; the reference has one scale, whose
+ * unconditional row drops bank, keypoints and audio together, pipelines/v_express_pipeline.py:368-370,404-406,548-550).
+ * vx_combine_units3 stands in for vx_combine_units and vx_guidance_rescale3 for vx_guidance_rescale in a guided step of
+ * a clip whose windows run three rows: gathered as above, unit_index int32 [n_windows][3][shards] naming the rows
+ * (u, m, c) of a window - u without any condition, m ("silent") with reference bank and keypoints but all-zero audio, c
+ * with everything; preds float32 [n_windows, c, f, hw] = g = u + s (m - u) + s_audio (c - m), evaluated as
+ * (u + s (m - u)) + s_audio * (c - m): where rows c and m hold equal bits g is what vx_combine_units writes for (u, m, s).
+ * vx_guidance_rescale3: preds[w] = g * (1 + phi (std(c) / std(g) - 1)) with the statistics of vx_guidance_rescale (the
+ * same workspace size, partials, block partition and ordered merge, so the same independence of shards, units and the
+ * number of windows); phi == 0 skips the statistics and writes exactly what vx_combine_units3 writes.  float32 only:
+ * both element builds carry the same code. */
+int vx_combine_units3(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c, int f, int hw,
+                      float guidance, float audio_guidance, float* preds, void* stream);
+int vx_guidance_rescale3(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c, int f,
+                         int hw, float guidance, float audio_guidance, float phi, float* workspace, int64_t ws_floats,
+                         float* preds, void* stream);
 /* per-frame mean-overlap + DDIM v-prediction step (eta=0):  v = sum_t (pred[term_slot[t]] / count) ;
  * latents[:, :, frame] = step(v).  terms: int32 [n_frames][max_terms][2] = (window slot, latent idx) or -1.
  * pipelines/v_express_pipeline.py:552-572 + diffusers DDIMScheduler.step.  */

@@ -1,0 +1,82 @@
+"""One rank of the two-rank runs of tests/test_audio_guidance_cpu.py (gloo, emulated kernels) and
+tests/test_gpu_audio_guidance.py (ranks folded onto one GPU, real kernels) (TEST INFRASTRUCTURE): the small-config
+denoising loop (DDIM) with three rows per window (audio_guidance_scale), the rescale and a guidance interval.
+usage (GPU, under torch.distributed.run): audio_guidance_worker.py OUT.pt GEOMETRY"""
+import os
+import sys
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+
+import cases  # noqa: E402
+import dist_gpu_worker as W  # noqa: E402
+import guidance_restated as G  # noqa: E402
+
+# name -> (F, context frames, overlap): one window = 3 units (on two ranks (u, m) | (c): the c row runs alone), two
+# windows = 6 units
+GEOMETRY = {"one_window": (8, 8, 2), "two_windows": (14, 8, 2)}
+# 3 DDIM steps of which the first 2 are guided (1 / 3 <= 0.67 and 2 / 3 <= 0.67; 3 / 3 is not)
+S_AUDIO, STEPS, PHI, END = 6.0, 3, 0.7, 0.67
+
+
+def run(geometry, latent=8, device="cpu", frame_shards=1):
+    """frame_shards = 1: whole units only, so that three units on two ranks leave one row alone on a rank."""
+    from v_express_amd import DDIMScheduler, ReferenceAttentionControl, ops, synth
+    from v_express_amd.context import get_context_scheduler
+    F, cf, co = GEOMETRY[geometry]
+    pipe = W.build_pipeline(device)
+    pipe.scheduler = sched = DDIMScheduler(**G.KWARGS)
+    pipe.frame_shards = frame_shards
+    unet, refnet = pipe.denoising_unet, pipe.reference_net
+    cfg = cases.unet_cfg(cases.SMALL)
+    inp = synth.synthetic_inputs(cfg, F, latent, latent, device=device)
+    # the pieces of VExpressPipeline.__call__ in its order (as dist_gpu_worker._run on CPU tensors)
+    writer = ReferenceAttentionControl(refnet, do_classifier_free_guidance=True, mode="write", fusion_blocks="full")
+    reader = ReferenceAttentionControl(unet, do_classifier_free_guidance=True, mode="read", fusion_blocks="full",
+                                       reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD)
+    refnet(inp["ref_latents"], timestep=0, encoder_hidden_states=torch.zeros(1, 1, 768, device=device),
+           return_dict=False)
+    reader.update(writer, True, dtype=unet.dtype)
+    sched.set_timesteps(STEPS)
+    windows = list(get_context_scheduler("uniform")(step=0, num_frames=F, context_size=cf, context_stride=1,
+                                                    context_overlap=co, closed_loop=False))
+    c0 = cfg.block_out_channels[0]
+    kps = ops.ncfhw_to_nhwc(inp["kps_features"], c0).view(2, F, latent * latent, c0)
+    audio = inp["audio_embeddings"].to(torch.bfloat16).contiguous()
+    lat = inp["latents"].clone().float()
+    pipe.denoise(lat, kps, audio, sched.timesteps.tolist(), windows, cases.GUIDANCE, guidance_rescale=PHI,
+                 guidance_end=END, audio_guidance_scale=S_AUDIO)
+    assert pipe.last_guidance["guided_steps"] == 2 and pipe.last_guidance["rows"] == ("u", "m", "c")
+    return lat.cpu(), dict(pipe.last_schedule), dict(pipe.last_guidance)
+
+
+def main(geometry, latent=8):
+    """CPU, under RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT: this rank's final latents and its two schedules."""
+    import torch.distributed as dist
+    import audio_guidance_restated as AG
+    from v_express_amd import ops
+    torch.set_num_threads(2)
+    dist.init_process_group("gloo")
+    W.emulate_kernels()
+    ops.guidance_rescale = G.guidance_rescale
+    ops.combine_units3 = AG.combine_units3
+    ops.guidance_rescale3 = AG.guidance_rescale3
+    out = run(geometry, latent)
+    dist.barrier()
+    dist.destroy_process_group()
+    return out
+
+
+if __name__ == "__main__":
+    import torch.distributed as dist
+    out_path, geometry = sys.argv[1], sys.argv[2]
+    dist.init_process_group(os.environ.get("VX_DIST_BACKEND", "gloo"))
+    torch.cuda.set_device(0)
+    lat, sched, guid = run(geometry, device="cuda")
+    if dist.get_rank() == 0:
+        torch.save(dict(latents=lat, schedule=sched), out_path)
+    dist.barrier()
+    dist.destroy_process_group()

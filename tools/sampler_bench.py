@@ -6,6 +6,7 @@ with a chosen sampler and step count (GPU box):
     python tools/sampler_bench.py --scheduler ddim-eta --eta 1.0 --steps 25
     python tools/sampler_bench.py --scheduler ddim --steps 25 --guidance-rescale 0.7 --guidance-end 0.6
     python tools/sampler_bench.py --scheduler ddim --steps 25 --init-video --strength 0.6 --mask lower-half
+    python tools/sampler_bench.py --scheduler ddim --steps 25 --audio-guidance-scale 6 [--guidance-scale 1]
 Prints one JSON line: ms per clip (host clock around whole clips, ending in a device synchronise), the denoise and decode
 milliseconds of the same clips (HIP events), and the average microseconds of the per-step update launch (HIP events
 around each `ops.overlap_ddim_step` / `ops.overlap_multistep_step` / `ops.overlap_ancestral_step` of one further,
@@ -18,7 +19,10 @@ the smallest and largest clip of the timed ones (`clip_ms_min`, `clip_ms_max`: H
 `denoise_ms` and of the clip) noised to the level of --strength, which also cuts the timesteps to the last
 int(steps * strength); --mask lower-half keeps the upper half of every frame (a `vx_known_blend` launch after every step,
 `blend_us`, and the composite post-process at the decode).  `postprocess_us` is the post-process launch of a decoded
-chunk (`postprocess`: which of the two ran), timed like the update launch."""
+chunk (`postprocess`: which of the two ran), timed like the update launch.
+--audio-guidance-scale s_a (with --guidance-scale s, default 3.5) runs the rows of a separate audio scale (`rows`: three per
+window for s > 1, the rows (m, c) for s <= 1 < s_a); `combine3_us` / `rescale3_us` are then the `ops.combine_units3` /
+`ops.guidance_rescale3` launches of a guided step, timed like their two-row siblings."""
 import argparse
 import json
 import os
@@ -39,6 +43,9 @@ def main():
     ap.add_argument("--guidance-rescale", type=float, default=0.0, help="phi of the CFG rescale")
     ap.add_argument("--guidance-start", type=float, default=0.0)
     ap.add_argument("--guidance-end", type=float, default=1.0)
+    ap.add_argument("--guidance-scale", type=float, default=3.5)
+    ap.add_argument("--audio-guidance-scale", type=float, default=None,
+                    help="a separate scale for the audio (three rows per window for --guidance-scale > 1)")
     ap.add_argument("--init-video", action="store_true", help="start from a synthetic init video (img2img)")
     ap.add_argument("--strength", type=float, default=1.0, help="run the last int(steps * strength) timesteps")
     ap.add_argument("--mask", choices=("none", "lower-half"), default="none",
@@ -112,6 +119,8 @@ def main():
             composite = (init_video, pixel_m.reshape(F, -1).to(dev).contiguous())
     # with the defaults the calls below are the ones this tool has always made (no begin_index, no known)
     extra = dict(begin_index=begin) if begin or args.init_video else {}
+    if args.audio_guidance_scale is not None:
+        extra["audio_guidance_scale"] = args.audio_guidance_scale
 
     def one_clip(ev=None):
         if ev:
@@ -124,7 +133,7 @@ def main():
             extra["known"] = (init, inp["latents"], latent_m)
         else:
             lat = inp["latents"] * pipe.scheduler.init_noise_sigma     # (1 but for Euler ancestral)
-        pipe.denoise(lat, kps_tokens, audio, timesteps, windows, 3.5, eta=eta, noise_seed=12345,
+        pipe.denoise(lat, kps_tokens, audio, timesteps, windows, args.guidance_scale, eta=eta, noise_seed=12345,
                      guidance_rescale=args.guidance_rescale, guidance_start=args.guidance_start,
                      guidance_end=args.guidance_end, **extra)
         if ev:
@@ -171,8 +180,15 @@ def main():
     post = "vae_postprocess_composite" if composite else "vae_postprocess"
     postprocess_us = round(update_launch_us(post)[1], 2)
     guided = pipe.last_guidance["guided_steps"]
-    rescale_us = round(update_launch_us("guidance_rescale")[1], 2) if args.guidance_rescale > 0 and guided else None
-    combine_us = round(update_launch_us("combine_units")[1], 2) if rescale_us is None or guided < args.steps else None
+    rows = pipe.last_guidance.get("rows")
+    three = rows == ("u", "m", "c")
+    rescaled = args.guidance_rescale > 0 and guided
+    rescale_us = round(update_launch_us("guidance_rescale")[1], 2) if rescaled and not three else None
+    rescale3_us = round(update_launch_us("guidance_rescale3")[1], 2) if rescaled and three else None
+    combine3_us = round(update_launch_us("combine_units3")[1], 2) if three and guided and not rescaled else None
+    combine_us = None
+    if (rescale_us is None and rescale3_us is None and combine3_us is None) or guided < args.steps:
+        combine_us = round(update_launch_us("combine_units")[1], 2)
     ddim_us = None
     if update == "overlap_ancestral_step":
         # the DDIM update of the same clip, timed the same way (eta = 0 on a DDIM scheduler of the same steps)
@@ -186,11 +202,13 @@ def main():
     print(json.dumps(dict(
         scheduler=args.scheduler, order=args.order if args.scheduler == "dpm" else None,
         eta=eta if args.scheduler == "ddim-eta" else None, steps=args.steps,
-        config="512x512, 16 frames (one window), CFG 3.5, synthetic weights, bf16", clips=args.clips,
+        config=f"512x512, 16 frames (one window), CFG {args.guidance_scale:g}, synthetic weights, bf16",
+        clips=args.clips,
         ms_per_clip=round(clip_ms, 2), denoise_ms=round(denoise_ms, 2), decode_ms=round(decode_ms, 2),
         frames_per_s=round(F * 1e3 / clip_ms, 3), update_launches=n_updates, update_us=round(update_us, 2),
         ddim_update_us=ddim_us, guidance_rescale=args.guidance_rescale, guidance_start=args.guidance_start,
         guidance_end=args.guidance_end, guided_steps=guided, rescale_us=rescale_us, combine_us=combine_us,
+        audio_guidance_scale=args.audio_guidance_scale, rows=rows, combine3_us=combine3_us, rescale3_us=rescale3_us,
         clip_ms_min=round(min(per_clip), 2), clip_ms_max=round(max(per_clip), 2), init_video=args.init_video,
         strength=args.strength, mask=args.mask, begin_index=begin, steps_run=len(timesteps), encode_ms=encode_ms,
         blend_launches=blend_launches, blend_us=None if blend_us is None else round(blend_us, 2), postprocess=post,

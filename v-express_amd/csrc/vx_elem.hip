@@ -126,6 +126,35 @@ __global__ void combine_units_kernel(const float* __restrict__ gathered, const i
     preds[(((size_t)wi * c + ch) * f + li) * hw + px] = u[ch] + guidance * (cnd[ch] - u[ch]);
 }
 
+// Three-row guidance (a separate audio scale): unit_index int32 [nW][3][S] names the rows (u, m, c) of a window - u without
+// any condition, m ("silent") with the reference bank and the keypoints but all-zero audio, c with everything - and the
+// prediction is g = u + s (m - u) + s_audio (c - m), evaluated as cfg_mix(u, m, s) + s_audio * (c - m): where c and m hold
+// equal bits this is the two-row kernel's u + s (m - u).
+__device__ __forceinline__ float cfg_mix(float u, float cnd, float guidance) { return u + guidance * (cnd - u); }
+
+__device__ __forceinline__ float cfg_mix3(float u, float m, float cnd, float guidance, float audio) {
+  return cfg_mix(u, m, guidance) + audio * (cnd - m);
+}
+
+__global__ void combine_units3_kernel(const float* __restrict__ gathered, const int32_t* __restrict__ unit_index,
+                                      int n_windows, int shards, int c, int f, int f_loc, int hw, float guidance,
+                                      float audio, float* __restrict__ preds) {
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // (window, li, pixel)
+  long total = (long)n_windows * f * hw;
+  if (idx >= total) return;
+  int px = (int)(idx % hw);
+  int li = (int)((idx / hw) % f);
+  int wi = (int)(idx / ((long)hw * f));
+  int j = li / f_loc;
+  long row = (long)(li - j * f_loc) * hw + px;
+  long unit_sz = (long)f_loc * hw * c;
+  const float* u = gathered + unit_index[(wi * 3 + 0) * shards + j] * unit_sz + row * c;
+  const float* m = gathered + unit_index[(wi * 3 + 1) * shards + j] * unit_sz + row * c;
+  const float* cnd = gathered + unit_index[(wi * 3 + 2) * shards + j] * unit_sz + row * c;
+  for (int ch = 0; ch < c; ++ch)
+    preds[(((size_t)wi * c + ch) * f + li) * hw + px] = cfg_mix3(u[ch], m[ch], cnd[ch], guidance, audio);
+}
+
 // CFG rescale (Lin et al. 2024, diffusers rescale_noise_cfg): per window, g = u + s (c - u) scaled by
 // 1 + phi (std(c) / std(g) - 1), std the unbiased one over the window's c * f * hw values.  Two launches.
 // (1) guidance_stats_kernel: one block per (window, frame of the window, chunk of GR_CHUNK pixels) forms the block's
@@ -133,10 +162,10 @@ __global__ void combine_units_kernel(const float* __restrict__ gathered, const i
 // the six floats to its own place of the workspace: no atomics, and the block partition does not depend on where a frame
 // came from (granules, ranks) or on the number of windows.  (2) guidance_scale_kernel: merges a window's partials in
 // ascending (frame, chunk) order with the pairwise formula in double precision, then writes g * factor.
+// ROWS = 2: the rows (u, c) of a window, g = cfg_mix(u, c, s).  ROWS = 3: the rows (u, m, c) of three-row guidance,
+// g = cfg_mix3(u, m, c, s, s_audio) against the std of the fully conditional row c; same partition, same merge.
 constexpr int GR_CHUNK = 1024;   // pixels per partial
 constexpr int GR_THREADS = 256;
-
-__device__ __forceinline__ float cfg_mix(float u, float cnd, float guidance) { return u + guidance * (cnd - u); }
 
 // sum of (a, b) over the block: wave-64 shuffles, then LDS across the waves, added in wave order; every thread gets it
 __device__ __forceinline__ void block_sum2(float& a, float& b, float* lds) {
@@ -161,35 +190,46 @@ __device__ __forceinline__ void block_sum2(float& a, float& b, float* lds) {
   }
 }
 
+// the guided prediction at one element of a window's rows: rows[0] = u, rows[ROWS - 1] = c, and rows[1] = m for ROWS = 3
+template <int ROWS>
+__device__ __forceinline__ float guided_value(const float* const* rows, long i, float guidance, float audio) {
+  if constexpr (ROWS == 2) return cfg_mix(rows[0][i], rows[1][i], guidance);
+  else return cfg_mix3(rows[0][i], rows[1][i], rows[2][i], guidance, audio);
+}
+
+template <int ROWS>
 __global__ __launch_bounds__(GR_THREADS) void guidance_stats_kernel(const float* __restrict__ gathered,
                                                                     const int32_t* __restrict__ unit_index, int shards,
                                                                     int c, int f, int f_loc, int hw, int chunks,
-                                                                    float guidance, float* __restrict__ partials) {
+                                                                    float guidance, float audio,
+                                                                    float* __restrict__ partials) {
   __shared__ float lds[2 * (GR_THREADS / 64)];
   const int chunk = blockIdx.x % chunks;
   const int li = (blockIdx.x / chunks) % f;
   const int wi = blockIdx.x / (chunks * f);
   const int j = li / f_loc;
   const long unit_sz = (long)f_loc * hw * c;
-  const float* ub = gathered + unit_index[(wi * 2 + 0) * shards + j] * unit_sz + (long)(li - j * f_loc) * hw * c;
-  const float* cb = gathered + unit_index[(wi * 2 + 1) * shards + j] * unit_sz + (long)(li - j * f_loc) * hw * c;
+  const float* rows[ROWS];
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r)
+    rows[r] = gathered + unit_index[(wi * ROWS + r) * shards + j] * unit_sz + (long)(li - j * f_loc) * hw * c;
+  const float* cb = rows[ROWS - 1];
   const int px0 = chunk * GR_CHUNK;
   const int px1 = min(px0 + GR_CHUNK, hw);
   const float n = (float)(px1 - px0) * (float)c;
   float sc = 0.f, sg = 0.f;
   for (int px = px0 + threadIdx.x; px < px1; px += GR_THREADS)
     for (int ch = 0; ch < c; ++ch) {
-      const float u = ub[(long)px * c + ch], cnd = cb[(long)px * c + ch];
-      sc += cnd;
-      sg += cfg_mix(u, cnd, guidance);
+      sc += cb[(long)px * c + ch];
+      sg += guided_value<ROWS>(rows, (long)px * c + ch, guidance, audio);
     }
   block_sum2(sc, sg, lds);
   const float mc = sc / n, mg = sg / n;
   float qc = 0.f, qg = 0.f;
   for (int px = px0 + threadIdx.x; px < px1; px += GR_THREADS)
     for (int ch = 0; ch < c; ++ch) {
-      const float u = ub[(long)px * c + ch], cnd = cb[(long)px * c + ch];
-      const float dc = cnd - mc, dg = cfg_mix(u, cnd, guidance) - mg;
+      const float dc = cb[(long)px * c + ch] - mc;
+      const float dg = guided_value<ROWS>(rows, (long)px * c + ch, guidance, audio) - mg;
       qc += dc * dc;
       qg += dg * dg;
     }
@@ -201,10 +241,11 @@ __global__ __launch_bounds__(GR_THREADS) void guidance_stats_kernel(const float*
   }
 }
 
+template <int ROWS>
 __global__ __launch_bounds__(GR_THREADS) void guidance_scale_kernel(const float* __restrict__ gathered,
                                                                     const int32_t* __restrict__ unit_index, int shards,
                                                                     int c, int f, int f_loc, int hw, int parts,
-                                                                    float guidance, float phi,
+                                                                    float guidance, float audio, float phi,
                                                                     const float* __restrict__ partials,
                                                                     float* __restrict__ preds) {
   __shared__ float factor_s;
@@ -238,10 +279,11 @@ __global__ __launch_bounds__(GR_THREADS) void guidance_scale_kernel(const float*
   const int j = li / f_loc;
   const long row = (long)(li - j * f_loc) * hw + px;
   const long unit_sz = (long)f_loc * hw * c;
-  const float* u = gathered + unit_index[(wi * 2 + 0) * shards + j] * unit_sz + row * c;
-  const float* cnd = gathered + unit_index[(wi * 2 + 1) * shards + j] * unit_sz + row * c;
+  const float* rows[ROWS];
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r) rows[r] = gathered + unit_index[(wi * ROWS + r) * shards + j] * unit_sz + row * c;
   for (int ch = 0; ch < c; ++ch)
-    preds[(((size_t)wi * c + ch) * f + li) * hw + px] = cfg_mix(u[ch], cnd[ch], guidance) * factor;
+    preds[(((size_t)wi * c + ch) * f + li) * hw + px] = guided_value<ROWS>(rows, ch, guidance, audio) * factor;
 }
 
 __global__ void overlap_ddim_kernel(float* latents, int c, int total_frames, int hw, const float* preds, int f_window,
@@ -601,6 +643,26 @@ extern "C" int64_t vx_guidance_rescale_ws_floats(int n_windows, int f, int hw) {
   return (int64_t)n_windows * f * ((hw + GR_CHUNK - 1) / GR_CHUNK) * 6;
 }
 
+// the two launches of vx_guidance_rescale (ROWS = 2) / vx_guidance_rescale3 (ROWS = 3), arguments already validated
+template <int ROWS>
+static int launch_guidance_rescale(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c,
+                                   int f, int hw, float guidance, float audio, float phi, float* workspace,
+                                   float* preds, void* stream, const char* stats_name, const char* name) {
+  const int chunks = (hw + GR_CHUNK - 1) / GR_CHUNK;
+  if (phi != 0.f) {
+    hipLaunchKernelGGL(guidance_stats_kernel<ROWS>, dim3((unsigned)(n_windows * f * chunks)), dim3(GR_THREADS), 0,
+                       (hipStream_t)stream, gathered, unit_index, shards, c, f, f / shards, hw, chunks, guidance, audio,
+                       workspace);
+    int rc = vx_check_launch(stats_name);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(guidance_scale_kernel<ROWS>,
+                     dim3((unsigned)(((long)f * hw + GR_THREADS - 1) / GR_THREADS), n_windows), dim3(GR_THREADS), 0,
+                     (hipStream_t)stream, gathered, unit_index, shards, c, f, f / shards, hw, f * chunks, guidance, audio,
+                     phi, workspace, preds);
+  return vx_check_launch(name);
+}
+
 extern "C" int vx_guidance_rescale(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c,
                                    int f, int hw, float guidance, float phi, float* workspace, int64_t ws_floats,
                                    float* preds, void* stream) {
@@ -611,19 +673,37 @@ extern "C" int vx_guidance_rescale(const float* gathered, const int32_t* unit_in
   VX_REQUIRE((long)c * f * hw >= 2, "vx_guidance_rescale: the standard deviation needs two values per window");
   VX_REQUIRE(ws_floats >= vx_guidance_rescale_ws_floats(n_windows, f, hw),
              "vx_guidance_rescale: workspace too small (vx_guidance_rescale_ws_floats)");
-  const int chunks = (hw + GR_CHUNK - 1) / GR_CHUNK;
-  VX_REQUIRE((long)n_windows * f * chunks <= 0x7fffffffL, "vx_guidance_rescale: too many partials");
-  if (phi != 0.f) {
-    hipLaunchKernelGGL(guidance_stats_kernel, dim3((unsigned)(n_windows * f * chunks)), dim3(GR_THREADS), 0,
-                       (hipStream_t)stream, gathered, unit_index, shards, c, f, f / shards, hw, chunks, guidance,
-                       workspace);
-    int rc = vx_check_launch("vx_guidance_rescale (statistics)");
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(guidance_scale_kernel, dim3((unsigned)(((long)f * hw + GR_THREADS - 1) / GR_THREADS), n_windows),
-                     dim3(GR_THREADS), 0, (hipStream_t)stream, gathered, unit_index, shards, c, f, f / shards, hw,
-                     f * chunks, guidance, phi, workspace, preds);
-  return vx_check_launch("vx_guidance_rescale");
+  VX_REQUIRE((long)n_windows * f * ((hw + GR_CHUNK - 1) / GR_CHUNK) <= 0x7fffffffL,
+             "vx_guidance_rescale: too many partials");
+  return launch_guidance_rescale<2>(gathered, unit_index, n_windows, shards, c, f, hw, guidance, 0.f, phi, workspace,
+                                    preds, stream, "vx_guidance_rescale (statistics)", "vx_guidance_rescale");
+}
+
+extern "C" int vx_combine_units3(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c,
+                                 int f, int hw, float guidance, float audio_guidance, float* preds, void* stream) {
+  VX_REQUIRE(gathered && unit_index && preds && n_windows > 0 && shards > 0 && c > 0 && f > 0 && hw > 0 &&
+                 f % shards == 0,
+             "vx_combine_units3: bad arguments");
+  hipLaunchKernelGGL(combine_units3_kernel, grid1d((long)n_windows * f * hw), dim3(256), 0, (hipStream_t)stream,
+                     gathered, unit_index, n_windows, shards, c, f, f / shards, hw, guidance, audio_guidance, preds);
+  return vx_check_launch("vx_combine_units3");
+}
+
+extern "C" int vx_guidance_rescale3(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c,
+                                    int f, int hw, float guidance, float audio_guidance, float phi, float* workspace,
+                                    int64_t ws_floats, float* preds, void* stream) {
+  VX_REQUIRE(gathered && unit_index && workspace && preds && n_windows > 0 && n_windows <= 65535 && shards > 0 && c > 0 &&
+                 f > 0 && hw > 0 && f % shards == 0,
+             "vx_guidance_rescale3: bad arguments");
+  VX_REQUIRE(phi >= 0.f && phi <= 1.f, "vx_guidance_rescale3: phi must lie in [0, 1]");
+  VX_REQUIRE((long)c * f * hw >= 2, "vx_guidance_rescale3: the standard deviation needs two values per window");
+  VX_REQUIRE(ws_floats >= vx_guidance_rescale_ws_floats(n_windows, f, hw),
+             "vx_guidance_rescale3: workspace too small (vx_guidance_rescale_ws_floats)");
+  VX_REQUIRE((long)n_windows * f * ((hw + GR_CHUNK - 1) / GR_CHUNK) <= 0x7fffffffL,
+             "vx_guidance_rescale3: too many partials");
+  return launch_guidance_rescale<3>(gathered, unit_index, n_windows, shards, c, f, hw, guidance, audio_guidance, phi,
+                                    workspace, preds, stream, "vx_guidance_rescale3 (statistics)",
+                                    "vx_guidance_rescale3");
 }
 
 extern "C" int vx_overlap_ddim_step(float* latents, int c, int total_frames, int hw, const float* preds, int f_window,

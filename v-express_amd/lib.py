@@ -162,6 +162,8 @@ def _load(path=None, element="bf16"):
     lib.vx_guidance_rescale_ws_floats.restype = i64
     lib.vx_guidance_rescale_ws_floats.argtypes = [i32, i32, i32]
     lib.vx_guidance_rescale.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, i64, vp, vp]
+    lib.vx_combine_units3.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp]
+    lib.vx_guidance_rescale3.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, i64, vp, vp]
     lib.vx_overlap_ddim_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, f32, f32, f32, f32, vp]
     lib.vx_overlap_multistep_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, f32, f32, f32, f32,
                                               f32, vp]

@@ -1361,6 +1361,44 @@ def guidance_rescale(gathered, unit_index, c, f, hw, guidance, phi, workspace, p
             "vx_guidance_rescale")
 
 
+def _check_units3(name, gathered, unit_index, c, f, hw, preds):
+    if unit_index.dim() != 3 or unit_index.shape[1] != 3:
+        raise ValueError(f"{name}: unit_index must be [nW, 3, S] (the rows u, m, c of every window)")
+    nW, _, S = unit_index.shape
+    if unit_index.dtype != torch.int32 or not unit_index.is_contiguous() or not gathered.is_contiguous():
+        raise TypeError(f"{name}: contiguous int32 index / contiguous gathered buffer expected")
+    if gathered.dtype != torch.float32 or preds.dtype != torch.float32 or not preds.is_contiguous():
+        raise TypeError(f"{name}: contiguous float32 gathered / preds expected")
+    if f % S or gathered.numel() % ((f // S) * hw * c) or preds.numel() != nW * c * f * hw:
+        raise ValueError(f"{name}: buffer sizes do not match (nW, c, f, hw, S)")
+    return nW, S
+
+
+def combine_units3(gathered, unit_index, c, f, hw, guidance, audio_guidance, preds):
+    """`combine_units` for three-row guidance: gathered fp32 [units_total, (f/S)*hw, c]; unit_index int32 [nW, 3, S] naming
+    the rows (u, m, c) of every window (m: reference + keypoints, zero audio) -> preds fp32 [nW, c, f, hw] =
+    u + guidance (m - u) + audio_guidance (c - m)."""
+    nW, S = _check_units3("combine_units3", gathered, unit_index, c, f, hw, preds)
+    L.check(_lib.vx_combine_units3(_ptr(gathered), _ptr(unit_index), nW, S, c, f, hw, float(guidance),
+                                   float(audio_guidance), _ptr(preds), _stream()), "vx_combine_units3")
+
+
+def guidance_rescale3(gathered, unit_index, c, f, hw, guidance, audio_guidance, phi, workspace, preds):
+    """`guidance_rescale` for three-row guidance: preds = g * (1 + phi (std(c) / std(g) - 1)) per window with
+    g = u + guidance (m - u) + audio_guidance (c - m) and c the fully conditional row; workspace as `guidance_rescale`
+    takes it (guidance_rescale_ws_floats(nW, f, hw) float32 elements)."""
+    nW, S = _check_units3("guidance_rescale3", gathered, unit_index, c, f, hw, preds)
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise TypeError("guidance_rescale3: contiguous float32 workspace expected")
+    if not 0.0 <= float(phi) <= 1.0:
+        raise ValueError(f"guidance_rescale3: phi must lie in [0, 1], got {phi}")
+    if workspace.numel() < guidance_rescale_ws_floats(nW, f, hw):
+        raise ValueError("guidance_rescale3: workspace smaller than guidance_rescale_ws_floats(nW, f, hw)")
+    L.check(_lib.vx_guidance_rescale3(_ptr(gathered), _ptr(unit_index), nW, S, c, f, hw, float(guidance),
+                                      float(audio_guidance), float(phi), _ptr(workspace), workspace.numel(),
+                                      _ptr(preds), _stream()), "vx_guidance_rescale3")
+
+
 def overlap_ddim_step(latents, preds, terms, frame_ids, counts, coef):
     """latents fp32 [1,C,F,h,w] updated in place for `frame_ids`; preds fp32 [slots, C, f, hw]."""
     _, c, F, h, w = latents.shape

@@ -19,6 +19,7 @@ transformers module.  The benchmark and the loop parity tests pass the prologue 
 """
 from typing import Callable, List, Optional, Union
 
+import math
 import os
 
 import torch
@@ -70,6 +71,37 @@ def check_guidance(guidance_rescale, guidance_start, guidance_end, n):
     if start > end:
         raise ValueError(f"guidance_start ({guidance_start}) must not exceed guidance_end ({guidance_end})")
     return phi, guided_steps(n, start, end)
+
+
+# The batch rows a window can run, as (bank row, keypoint row, audio row) of the CFG-layout conditioning (row 0 zeros,
+# row 1 real): "u" drops everything, "m" ("silent") keeps the reference bank and the keypoints and drops the audio, "c"
+# keeps everything.
+GUIDANCE_ROWS = {"u": (0, 0, 0), "m": (1, 1, 0), "c": (1, 1, 1)}
+
+
+def check_audio_guidance(audio_guidance_scale):
+    """Validates `audio_guidance_scale`; returns it as a float, or None."""
+    if audio_guidance_scale is None:
+        return None
+    s_a = float(audio_guidance_scale)
+    if not (math.isfinite(s_a) and s_a >= 0.0):
+        raise ValueError(f"audio_guidance_scale must be a finite number >= 0, got {audio_guidance_scale}")
+    return s_a
+
+
+def guidance_rows(guidance_scale, audio_guidance_scale=None):
+    """The rows a guided step runs per window for the scales s = guidance_scale and s_a = audio_guidance_scale, whose
+    guided prediction is u + s (m - u) + s_a (c - m):
+      s_a None or == s  -> ("u", "c") for s > 1, else ("c",): the formula is u + s (c - u), the one-scale route;
+      s > 1, s_a != s   -> ("u", "m", "c");
+      s <= 1, s_a > 1   -> ("m", "c"): m + s_a (c - m), audio guidance at the cost of one-scale CFG;
+      s <= 1, s_a <= 1  -> ("c",): no guidance."""
+    s_a = check_audio_guidance(audio_guidance_scale)
+    if s_a is None or s_a == guidance_scale:
+        return ("u", "c") if guidance_scale > 1.0 else ("c",)
+    if guidance_scale > 1.0:
+        return ("u", "m", "c")
+    return ("m", "c") if s_a > 1.0 else ("c",)
 
 
 def check_init(init_video, init_latents, mask, video_length, height, width, scale, channels=4):
@@ -140,7 +172,9 @@ class VExpressPipeline:
         # the schedule the last denoise() call chose (for logs / bench.py): dict(kind, frame_shards, mixed_shards, ...)
         self.last_schedule = {}
         # the guidance controls of the last denoise() call: dict(guided_steps, steps, rescale, unguided_schedule), the
-        # last one the last_schedule-style dict of the conditional-only plan of its unguided steps, or None
+        # last one the last_schedule-style dict of the conditional-only plan of its unguided steps, or None.  A call that
+        # passes audio_guidance_scale also finds `rows` (guidance_rows: ("u", "c"), ("u", "m", "c"), ("m", "c") or
+        # ("c",)) and `audio_scale` in it; without the keyword the dict is what it was before the keyword existed
         self.last_guidance = {}
         # init-video sampling of the last denoise() call: dict(begin_index, masked, blend_launches) - the step index the
         # loop started at, whether a latent mask was blended in after every step, and the vx_known_blend launches of the
@@ -295,7 +329,9 @@ class VExpressPipeline:
         """The static plan of one kind of timestep: which (window, half) units this rank computes, in which UNet calls,
         and where they land in the exchange buffer.  `half_rows`: the row of the kps / audio tensors and of the reference
         banks that each half of the plan uses - [0, 1] under classifier-free guidance, [0] without, [1] for the
-        conditional half alone of a CFG clip (an unguided step).  Collective (`dc.frame_shard`): every rank builds it.
+        conditional half alone of a CFG clip (an unguided step).  An entry may also name the three separately, as
+        (bank row, keypoint row, audio row): GUIDANCE_ROWS["m"] = (1, 1, 0) is the silent row of three-row guidance (an
+        int r stands for (r, r, r)).  Collective (`dc.frame_shard`): every rank builds it.
         Returns dict(calls, local, uidx, max_slots, schedule)."""
         unet, dc, dev = self.denoising_unet, self.dist, latents.device
         _, C, F, H, W = latents.shape
@@ -303,6 +339,7 @@ class VExpressPipeline:
         f = len(windows[0])
         nW = len(windows)
         halves_n = len(half_rows)
+        row_of = [r if isinstance(r, tuple) else (r, r, r) for r in half_rows]      # (bank, kps, audio) of each half
         win_ids_long = win_ids.long()
         min_hw = (H // 8) * (W // 8)
         S = self.frame_shards or choose_frame_shards(nW, dc.world_size, f, min_hw, halves_n)
@@ -366,11 +403,12 @@ class VExpressPipeline:
                 rows = [(wi, hlf) for wi, halves in group for hlf in halves]      # batch rows of the call, in order
                 kps_l, ehs_l = [], []
                 for wi, halves in group:
-                    hsel = torch.tensor([half_rows[hlf] for hlf in halves], device=dev)
+                    ksel = torch.tensor([row_of[hlf][1] for hlf in halves], device=dev)
+                    asel = torch.tensor([row_of[hlf][2] for hlf in halves], device=dev)
                     ids_long = win_ids_long[wi][lo:lo + f_loc]
-                    kps_l.append(kps_tokens.index_select(0, hsel).index_select(1, ids_long)
+                    kps_l.append(kps_tokens.index_select(0, ksel).index_select(1, ids_long)
                                  .reshape(len(halves) * f_loc, hw, -1))
-                    e = audio.index_select(0, hsel).index_select(1, ids_long)
+                    e = audio.index_select(0, asel).index_select(1, ids_long)
                     ehs_l.append(e.reshape(-1, e.shape[-1]))
                 kps = torch.cat(kps_l, dim=0).contiguous()
                 ehs = torch.cat(ehs_l, dim=0).contiguous()
@@ -380,15 +418,15 @@ class VExpressPipeline:
                 s0 = min(slot for (r, slot) in unit_slots[rows[0]] if r == dc.rank)
                 n_slots = len(rows) * (G // Sc)
                 # the audio K | V of all 16 transformer blocks is step-invariant: once per clip and call
-                bank_rows = [half_rows[hlf] for _, hlf in rows]
+                bank_rows = [row_of[hlf][0] for _, hlf in rows]
                 calls.append((bank_rows, gathers, kps, ehs, unet.precompute_audio_kv(ehs),
-                              [audio_is_zero[r] for r in bank_rows], f_loc, shard, s0, n_slots))
+                              [audio_is_zero[row_of[hlf][2]] for _, hlf in rows], f_loc, shard, s0, n_slots))
         return dict(calls=calls, local=local, uidx=uidx, max_slots=max_slots, schedule=schedule)
 
     @_in_unet_element_type
     def denoise(self, latents, kps_tokens, audio, timesteps, windows, guidance_scale, callback=None,
                 callback_steps=1, *, begin_index=None, eta=0.0, noise_seed=None, guidance_rescale=0.0,
-                guidance_start=0.0, guidance_end=1.0, known=None):
+                guidance_start=0.0, guidance_end=1.0, known=None, audio_guidance_scale=None):
         """pipelines/v_express_pipeline.py:526-583.  latents fp32 [1,4,F,h,w] (device, updated in place);
         kps_tokens bf16 [b, F, hw, C0]; audio bf16 [b, F, n_ctx, 768] with b = 2 (uncond, cond) under classifier-free
         guidance (guidance_scale > 1, :443) and b = 1 (the conditional row only) without.
@@ -401,6 +439,11 @@ class VExpressPipeline:
         i / N >= guidance_start and (i + 1) / N <= guidance_end, any other step computes the conditional rows only and
         takes them as the prediction; guidance_rescale = phi > 0 scales each window's guided prediction g by
         1 + phi (std(cond) / std(g) - 1) before the overlap sum (diffusers' rescale_noise_cfg, vx_guidance_rescale).
+        A separate audio scale: audio_guidance_scale = s_a (None = guidance_scale) guides on the audio apart from the
+        reference image and the keypoints, g = u + s (m - u) + s_a (c - m) with m the row that keeps bank and keypoints
+        and drops the audio; the rows a guided step runs are guidance_rows(s, s_a) - three per window for s > 1 and
+        s_a != s (vx_combine_units3 / vx_guidance_rescale3), (m, c) with guidance s_a for s <= 1 < s_a; both need the
+        b = 2 conditioning.  The rescale is towards std(c); an unguided step runs c alone, and neither scale applies.
         Init-video sampling (every sampler): known = (init, noise, m) - the clip's clean latents and the N(0,1) tensor,
         fp32 shaped like `latents`, and the latent mask fp32 [F, h*w] in [0, 1] (1 = regenerate, 0 = keep) or None.  The
         loop then starts from a_b init + s_b noise, b = begin_index (what `latents` held is not read), with (a_j, s_j)
@@ -411,6 +454,7 @@ class VExpressPipeline:
         latents).  m = None is plain img2img: no launch after the start."""
         kind = self._sampler(eta)
         guidance_rescale, guided = check_guidance(guidance_rescale, guidance_start, guidance_end, len(timesteps))
+        row_names = guidance_rows(guidance_scale, audio_guidance_scale)
         init = noise = kmask = None
         if known is not None:
             init, noise, kmask = known
@@ -449,11 +493,17 @@ class VExpressPipeline:
         terms = terms.to(dev)
         frame_ids = torch.tensor(sf, dtype=torch.int32, device=dev)
         counts = torch.tensor([float(plan["counts"][fr]) for fr in sf], dtype=torch.float32, device=dev)
-        do_cfg = guidance_scale > 1.0
-        halves_n = 2 if do_cfg else 1
-        if kps_tokens.shape[0] != halves_n or audio.shape[0] != halves_n:
-            raise ValueError(f"guidance_scale={guidance_scale} needs {halves_n} batch row(s) of kps features / audio "
-                             f"embeddings, got {kps_tokens.shape[0]} / {audio.shape[0]}")
+        do_cfg = len(row_names) > 1                   # a guided step combines rows
+        three = len(row_names) == 3
+        # the one scale of a two-row combine: (m, c) is guided by the audio scale
+        scale2 = float(audio_guidance_scale) if row_names == ("m", "c") else guidance_scale
+        cond_rows = 2 if do_cfg else 1
+        if kps_tokens.shape[0] != cond_rows or audio.shape[0] != cond_rows:
+            what = f"guidance_scale={guidance_scale}"
+            if row_names in (("m", "c"), ("u", "m", "c")):
+                what += f" with audio_guidance_scale={audio_guidance_scale} (the silent row takes the zero-audio row 0)"
+            raise ValueError(f"{what} needs {cond_rows} batch row(s) of kps features / audio embeddings, got "
+                             f"{kps_tokens.shape[0]} / {audio.shape[0]}")
         if not do_cfg:                                # nothing to rescale, nothing to switch off
             guidance_rescale, guided = 0.0, [True] * len(timesteps)
         # which CFG halves carry all-zero audio tokens (the unconditional half, :403-405): one device reduction per clip
@@ -461,7 +511,9 @@ class VExpressPipeline:
         # one plan for the guided steps (every step, by default); a second one, the conditional half alone, only when
         # some step runs without guidance.  Both are built on every rank, before the loop (the shard groups are collective)
         preds = torch.empty((nW, C, f, hw), device=dev, dtype=torch.float32)
-        plan_g = self._unit_plan(latents, kps_tokens, audio, audio_is_zero, windows, win_ids, list(range(halves_n)))
+        # (the one-scale routes name their rows by index, as they always have; a silent row needs the triple)
+        half_rows = [GUIDANCE_ROWS[r] for r in row_names] if "m" in row_names else list(range(cond_rows))
+        plan_g = self._unit_plan(latents, kps_tokens, audio, audio_is_zero, windows, win_ids, half_rows)
         self.last_schedule = plan_g["schedule"]
         plan_c = None
         if not all(guided):
@@ -469,6 +521,8 @@ class VExpressPipeline:
         self.last_guidance = dict(guided_steps=sum(guided) if do_cfg else 0, steps=len(timesteps),
                                   rescale=guidance_rescale,
                                   unguided_schedule=None if plan_c is None else plan_c["schedule"])
+        if audio_guidance_scale is not None:
+            self.last_guidance.update(rows=row_names, audio_scale=float(audio_guidance_scale))
         rescale_ws = None
         if guidance_rescale > 0.0 and any(guided):
             rescale_ws = torch.empty(ops.guidance_rescale_ws_floats(nW, f, hw), device=dev, dtype=torch.float32)
@@ -506,13 +560,20 @@ class VExpressPipeline:
                 # a call's units occupy consecutive send slots, in row order: one strided pack per call
                 ops.pack_rows(out, C, local[s0:s0 + n_slots])
             gathered = dc.all_gather_units(local, max_slots)          # [world, max_slots, (f/G)*hw, C]
-            if rescale_ws is not None and guided[i]:
+            if three and guided[i]:
+                # u + s (m - u) + s_a (c - m) of every window, rescaled towards the conditional row's spread or not
+                if rescale_ws is not None:
+                    ops.guidance_rescale3(gathered, uidx, C, f, hw, guidance_scale, audio_guidance_scale,
+                                          guidance_rescale, rescale_ws, preds)
+                else:
+                    ops.combine_units3(gathered, uidx, C, f, hw, guidance_scale, audio_guidance_scale, preds)
+            elif rescale_ws is not None and guided[i]:
                 # the CFG combine with each window's prediction rescaled towards the conditional one's spread
-                ops.guidance_rescale(gathered, uidx, C, f, hw, guidance_scale, guidance_rescale, rescale_ws, preds)
+                ops.guidance_rescale(gathered, uidx, C, f, hw, scale2, guidance_rescale, rescale_ws, preds)
             else:
                 # CFG combine of every window in one launch (:548-550; without CFG, and in an unguided step, the
                 # conditional prediction itself)
-                ops.combine_units(gathered, uidx, C, f, hw, guidance_scale if do_cfg and guided[i] else 1.0, preds)
+                ops.combine_units(gathered, uidx, C, f, hw, scale2 if do_cfg and guided[i] else 1.0, preds)
             if multistep:
                 ops.overlap_multistep_step(latents, preds, terms, frame_ids, counts, x0_hist, coefs[i])
             elif ancestral:
@@ -570,8 +631,12 @@ class VExpressPipeline:
                  reference_latents=None, kps_features=None, audio_embeddings=None, latents=None,
                  noise_seed: Optional[int] = None, output_device="cpu", decode=True, guidance_rescale: float = 0.0,
                  guidance_start: float = 0.0, guidance_end: float = 1.0, init_video=None, init_latents=None,
-                 mask=None, composite=True, **kwargs):
-        """Init-video sampling (diffusers' img2img / inpaint semantics for a 4-channel UNet): `init_video` fp32
+                 mask=None, composite=True, audio_guidance_scale: Optional[float] = None, **kwargs):
+        """A separate audio scale: `audio_guidance_scale` = s_a (default None: the one scale of `guidance_scale` = s)
+        guides on the audio apart from the reference image and the keypoints: u + s (m - u) + s_a (c - m), m the
+        prediction with bank and keypoints but silent audio (three rows per window for s > 1 and s_a != s; the rows
+        (m, c) for s <= 1 < s_a).  The prologue runs in the CFG layout whenever either scale exceeds 1.
+        Init-video sampling (diffusers' img2img / inpaint semantics for a 4-channel UNet): `init_video` fp32
         [1, 3, F, H, W] in [0, 1] (VAE-encoded here; needs v_express_amd.AutoencoderKL) or `init_latents`
         [1, 4, F, h, w] (clean, already scaled) makes the loop start from the clip noised to the level of `strength`
         instead of from pure noise; `mask` ([F or 1, 1, H, W] or [F or 1, H, W], float or bool in [0, 1]; 1 =
@@ -582,6 +647,7 @@ class VExpressPipeline:
         # that do not fit the clip fail here, before the prologue
         kind = self._sampler(eta)
         check_guidance(guidance_rescale, guidance_start, guidance_end, max(int(num_inference_steps), 1))
+        audio_guidance_scale = check_audio_guidance(audio_guidance_scale)
         pixel_mask = check_init(init_video, init_latents, mask, video_length, height, width, self.vae_scale_factor,
                                 self.denoising_unet.in_channels)
         if init_video is not None and not hasattr(self.vae, "encode_video"):
@@ -589,7 +655,8 @@ class VExpressPipeline:
                                       "v_express_amd.AutoencoderKL and load encoder.* / quant_conv.*, or pass "
                                       "init_latents=[1,4,F,h/8,w/8] (already scaled by 0.18215)")
         dev = self.device
-        do_cfg = guidance_scale > 1.0
+        # the CFG layout of banks and conditioning (row 0 zeros, row 1 real): whenever a guided step combines rows
+        do_cfg = len(guidance_rows(guidance_scale, audio_guidance_scale)) > 1
         # timesteps (retrieve_timesteps + get_timesteps, :448-449)
         self.scheduler.set_timesteps(num_inference_steps)
         init_t = min(int(num_inference_steps * strength), num_inference_steps)
@@ -664,7 +731,8 @@ class VExpressPipeline:
             ev[0].record()
         self.denoise(lat, kps_tokens, audio, timesteps, windows, guidance_scale, callback, callback_steps or 1,
                      begin_index=begin_index, eta=eta, noise_seed=noise_seed, guidance_rescale=guidance_rescale,
-                     guidance_start=guidance_start, guidance_end=guidance_end, known=known)
+                     guidance_start=guidance_start, guidance_end=guidance_end, known=known,
+                     audio_guidance_scale=audio_guidance_scale)
         if timed:
             ev[1].record()
         reader.clear()
