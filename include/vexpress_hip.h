@@ -470,6 +470,18 @@ int vx_overlap_ancestral_step(float* latents, int c, int total_frames, int hw, c
                               const int32_t* terms, int max_terms, const int32_t* frame_ids, const float* count,
                               int n_frames, float alpha_s, float sigma_s, float c_x, float c_0, float c_z,
                               uint32_t seed_lo, uint32_t seed_hi, int step_index, void* stream);
+/* Weighted window blend of the overlap (`overlap_blend` = "linear", "pyramid" or a per-position profile; the reference
+ * has only the mean, each window's prediction divided by the coverage count: pipelines/v_express_pipeline.py:552-572):
+ *   out[ch, i, px] = sum over t, in ascending t, of weights[i][t] * preds[slot_t, ch, li_t, px]
+ * preds: float32 [slots, c, f_window, hw] as the update kernels read it; terms: int32 [n_frames][max_terms][2] = (window
+ * slot, latent idx), slot < 0 = skip; weights: float32 [n_frames][max_terms], a frame's weights normalised to sum 1 by
+ * the host (context.weighted_overlap_plan); out: float32 [c, n_frames, hw].  Every product and every sum is rounded to
+ * float32 separately (no fma contraction) and the first valid term initialises the sum: a float32 host expression gives
+ * the same bits.  A pre-pass of a timestep: the update kernels then run on out viewed as [1, c, n_frames, hw] with the
+ * trivial plan terms[i] = (0, i), max_terms = 1, count = 1 (p / 1.0f is exact), so samplers, x0 history and noise stream
+ * are untouched.  hw % 4 == 0; preds / out 16-byte aligned.  float32 only: both element builds carry the same code. */
+int vx_overlap_blend(const float* preds, int c, int f_window, int hw, const int32_t* terms, const float* weights,
+                     int max_terms, int n_frames, float* out, void* stream);
 /* Known-region blend of init-video sampling (img2img / inpainting for a 4-channel UNet):
  *   mask != NULL:  latents = m * latents + (1 - m) * (a * init + s * noise)      (m = 1 regenerates, m = 0 keeps)
  *   mask == NULL:  latents = a * init + s * noise                                (the start latents; the old value is not read)

@@ -22,7 +22,11 @@ int(steps * strength); --mask lower-half keeps the upper half of every frame (a 
 chunk (`postprocess`: which of the two ran), timed like the update launch.
 --audio-guidance-scale s_a (with --guidance-scale s, default 3.5) runs the rows of a separate audio scale (`rows`: three per
 window for s > 1, the rows (m, c) for s <= 1 < s_a); `combine3_us` / `rescale3_us` are then the `ops.combine_units3` /
-`ops.guidance_rescale3` launches of a guided step, timed like their two-row siblings."""
+`ops.guidance_rescale3` launches of a guided step, timed like their two-row siblings.
+--frames F --context-frames f --context-overlap o --context-schedule uniform|uniform_fit choose the clip length and its
+windows (defaults: 16 frames in one window of 16, overlap 4, `uniform`); --overlap-blend mean|linear|pyramid the stitch of
+overlapping windows - a weighted blend adds one `ops.overlap_blend` launch per step (`overlap_blend_us`, timed like the
+update launch, whose own time is then that of the trivial one-term plan)."""
 import argparse
 import json
 import os
@@ -50,6 +54,11 @@ def main():
     ap.add_argument("--strength", type=float, default=1.0, help="run the last int(steps * strength) timesteps")
     ap.add_argument("--mask", choices=("none", "lower-half"), default="none",
                     help="with --init-video: regenerate the lower half of every frame, keep the upper half")
+    ap.add_argument("--frames", type=int, default=16, help="clip length")
+    ap.add_argument("--context-frames", type=int, default=16)
+    ap.add_argument("--context-overlap", type=int, default=4)
+    ap.add_argument("--context-schedule", choices=("uniform", "uniform_fit"), default="uniform")
+    ap.add_argument("--overlap-blend", choices=("mean", "linear", "pyramid"), default="mean")
     ap.add_argument("--clips", type=int, default=5, help="timed clips")
     ap.add_argument("--warmup", type=int, default=1)
     args = ap.parse_args()
@@ -63,12 +72,12 @@ def main():
         raise SystemExit("sampler_bench.py measures on the GPU: no device visible")
     import v_express_amd as vx
     from v_express_amd import ops, synth
-    from v_express_amd.context import uniform
+    from v_express_amd.context import get_context_scheduler
     from v_express_amd.pipeline import latent_mask
     dev, elem = torch.device("cuda", 0), torch.bfloat16
     torch.cuda.set_device(dev)
     cfg, vcfg = synth.UNetConfig(), synth.VaeConfig()
-    F, h = 16, 64
+    F, h = args.frames, 64
     unet = vx.UNet3DConditionModel(cfg).to(dev).to(elem)
     refnet = vx.UNet2DConditionModel(cfg).to(dev).to(elem)
     vae = (vx.AutoencoderKL if args.init_video else vx.AutoencoderKLDecoder)(vcfg).to(dev).to(elem)
@@ -103,8 +112,9 @@ def main():
     timesteps = sched.timesteps[begin:].tolist()
     if not timesteps:
         ap.error("--strength leaves no timestep to run")
-    windows = list(uniform(step=0, num_frames=F, context_size=16, context_stride=1, context_overlap=4,
-                           closed_loop=False))
+    windows = list(get_context_scheduler(args.context_schedule)(
+        step=0, num_frames=F, context_size=args.context_frames, context_stride=1, context_overlap=args.context_overlap,
+        closed_loop=False))
     c0 = cfg.block_out_channels[0]
     kps_tokens = ops.ncfhw_to_nhwc(inp["kps_features"], c0).view(2, F, h * h, c0)
     audio = inp["audio_embeddings"].to(elem).contiguous()
@@ -121,6 +131,8 @@ def main():
     extra = dict(begin_index=begin) if begin or args.init_video else {}
     if args.audio_guidance_scale is not None:
         extra["audio_guidance_scale"] = args.audio_guidance_scale
+    if args.overlap_blend != "mean":
+        extra["overlap_blend"] = args.overlap_blend
 
     def one_clip(ev=None):
         if ev:
@@ -177,6 +189,7 @@ def main():
         return len(marks), 1e3 * sum(s.elapsed_time(e) for s, e in marks) / max(len(marks), 1)
     n_updates, update_us = update_launch_us(update)
     blend_launches, blend_us = update_launch_us("known_blend") if args.init_video else (0, None)
+    wblend_launches, wblend_us = update_launch_us("overlap_blend") if args.overlap_blend != "mean" else (0, None)
     post = "vae_postprocess_composite" if composite else "vae_postprocess"
     postprocess_us = round(update_launch_us(post)[1], 2)
     guided = pipe.last_guidance["guided_steps"]
@@ -202,7 +215,8 @@ def main():
     print(json.dumps(dict(
         scheduler=args.scheduler, order=args.order if args.scheduler == "dpm" else None,
         eta=eta if args.scheduler == "ddim-eta" else None, steps=args.steps,
-        config=f"512x512, 16 frames (one window), CFG {args.guidance_scale:g}, synthetic weights, bf16",
+        config=f"512x512, {F} frames ({'one window' if len(windows) == 1 else f'{len(windows)} windows'}), "
+               f"CFG {args.guidance_scale:g}, synthetic weights, bf16",
         clips=args.clips,
         ms_per_clip=round(clip_ms, 2), denoise_ms=round(denoise_ms, 2), decode_ms=round(decode_ms, 2),
         frames_per_s=round(F * 1e3 / clip_ms, 3), update_launches=n_updates, update_us=round(update_us, 2),
@@ -212,7 +226,10 @@ def main():
         clip_ms_min=round(min(per_clip), 2), clip_ms_max=round(max(per_clip), 2), init_video=args.init_video,
         strength=args.strength, mask=args.mask, begin_index=begin, steps_run=len(timesteps), encode_ms=encode_ms,
         blend_launches=blend_launches, blend_us=None if blend_us is None else round(blend_us, 2), postprocess=post,
-        postprocess_us=postprocess_us, build=vx.lib.lib.vx_build_id().decode())))
+        postprocess_us=postprocess_us, frames=F, context_frames=args.context_frames,
+        context_overlap=args.context_overlap, context_schedule=args.context_schedule, windows=len(windows),
+        overlap_blend=args.overlap_blend, overlap_blend_launches=wblend_launches,
+        overlap_blend_us=None if wblend_us is None else round(wblend_us, 2), build=vx.lib.lib.vx_build_id().decode())))
 
 
 if __name__ == "__main__":

@@ -397,6 +397,41 @@ __global__ void overlap_ancestral_kernel(float* latents, int c, int total_frames
   *lp = out;
 }
 
+// Weighted window blend (`overlap_blend`): out[ch, i, px] = sum over the terms t of frame i, in ascending t, of
+// weights[i][t] * preds[slot_t, ch, li_t, px], terms / weights as the update kernels read theirs (slot < 0 = skip).  Every
+// product and every sum is rounded to float32 on its own (__fmul_rn / __fadd_rn: never contracted to an fma) and the first
+// valid term initialises the sum, so a float32 host expression reproduces the bits.  One thread per (frame, channel, pixel
+// quad): float4 loads and stores (hw % 4 == 0, 16-byte aligned rows).  A frame without a valid term receives zeros.
+__global__ void overlap_blend_kernel(const float* __restrict__ preds, int c, int f_window, int hw,
+                                     const int32_t* __restrict__ terms, const float* __restrict__ weights,
+                                     int max_terms, int n_frames, float* __restrict__ out) {
+  const int hq = hw >> 2;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // (frame, channel, pixel quad)
+  const long total = (long)n_frames * c * hq;
+  if (idx >= total) return;
+  const int q = (int)(idx % hq);
+  const int ch = (int)((idx / hq) % c);
+  const int fs = (int)(idx / ((long)hq * c));
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  bool first = true;
+  for (int t = 0; t < max_terms; ++t) {
+    const int slot = terms[((long)fs * max_terms + t) * 2 + 0];
+    const int li = terms[((long)fs * max_terms + t) * 2 + 1];
+    if (slot < 0) continue;
+    const float wt = weights[(long)fs * max_terms + t];
+    const float4 p = *reinterpret_cast<const float4*>(preds + (((size_t)slot * c + ch) * f_window + li) * hw + 4 * q);
+    const float4 term = make_float4(__fmul_rn(wt, p.x), __fmul_rn(wt, p.y), __fmul_rn(wt, p.z), __fmul_rn(wt, p.w));
+    if (first) {
+      v = term;
+    } else {
+      v.x = __fadd_rn(v.x, term.x); v.y = __fadd_rn(v.y, term.y);
+      v.z = __fadd_rn(v.z, term.z); v.w = __fadd_rn(v.w, term.w);
+    }
+    first = false;
+  }
+  *reinterpret_cast<float4*>(out + ((size_t)ch * n_frames + fs) * hw + 4 * q) = v;
+}
+
 // Known-region blend of init-video sampling: latents = m * latents + (1 - m) * (a * init + s * noise), m the latent mask
 // [total_frames, hw] shared by the channels (1 = regenerate, 0 = keep); MASKED = false writes a * init + s * noise (the
 // start latents) and does not read the old value.  One thread per (channel, frame, pixel quad): float4 loads and stores
@@ -743,6 +778,18 @@ extern "C" int vx_overlap_ancestral_step(float* latents, int c, int total_frames
                      (hipStream_t)stream, latents, c, total_frames, hw, preds, f_window, terms, max_terms, frame_ids,
                      count, n_frames, alpha_s, sigma_s, c_x, c_0, c_z, seed_lo, seed_hi, step_index);
   return vx_check_launch("vx_overlap_ancestral_step");
+}
+
+extern "C" int vx_overlap_blend(const float* preds, int c, int f_window, int hw, const int32_t* terms,
+                                const float* weights, int max_terms, int n_frames, float* out, void* stream) {
+  VX_REQUIRE(preds && terms && weights && out && c > 0 && f_window > 0 && hw > 0 && max_terms > 0 && n_frames > 0 &&
+                 (hw % 4) == 0 && ((uintptr_t)preds % 16) == 0 && ((uintptr_t)out % 16) == 0,
+             "vx_overlap_blend: bad arguments (hw %% 4 == 0 and 16-byte aligned preds / out required)");
+  const long quads = (long)n_frames * c * (hw / 4);
+  VX_REQUIRE(quads <= 0x7fffffffL * 256L, "vx_overlap_blend: too many elements for one launch");
+  hipLaunchKernelGGL(overlap_blend_kernel, grid1d(quads), dim3(256), 0, (hipStream_t)stream, preds, c, f_window, hw,
+                     terms, weights, max_terms, n_frames, out);
+  return vx_check_launch("vx_overlap_blend");
 }
 
 extern "C" int vx_known_blend(float* latents, const float* init, const float* noise, const float* mask, int c,

@@ -169,6 +169,7 @@ def _load(path=None, element="bf16"):
                                               f32, vp]
     lib.vx_overlap_ancestral_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, f32, f32, f32, f32,
                                               f32, C.c_uint32, C.c_uint32, i32, vp]
+    lib.vx_overlap_blend.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp]
     lib.vx_known_blend.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, vp]
     lib.vx_vae_postprocess_composite.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp]
     lib.vx_ncfhw_to_nhwc.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]

@@ -1438,6 +1438,29 @@ def overlap_ancestral_step(latents, preds, terms, frame_ids, counts, coef, seed,
                                            _stream()), "vx_overlap_ancestral_step")
 
 
+def overlap_blend(preds, terms, weights, out):
+    """Weighted window blend (vx_overlap_blend): preds fp32 [slots, C, f, hw]; terms int32 [F, max_terms, 2] = (window
+    slot, latent idx) or -1; weights fp32 [F, max_terms] (context.weighted_overlap_plan) -> out fp32 [C, F, hw] (or
+    [1, C, F, h, w]) = sum_t weights[:, t] * preds[term t], every product and sum rounded to float32, in term order."""
+    for t, name in ((preds, "preds"), (weights, "weights"), (out, "out")):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError(f"overlap_blend: contiguous float32 {name} expected")
+    if terms.dtype != torch.int32 or not terms.is_contiguous():
+        raise TypeError("overlap_blend: contiguous int32 terms expected")
+    if preds.dim() != 4 or terms.dim() != 3 or terms.shape[2] != 2 or terms.shape[1] < 1:
+        raise ValueError("overlap_blend: preds must be [slots, C, f, hw] and terms [F, max_terms, 2]")
+    _, c, f, hw = preds.shape
+    n, max_terms = terms.shape[0], terms.shape[1]
+    if tuple(weights.shape) != (n, max_terms):
+        raise ValueError(f"overlap_blend: weights must be [F, max_terms] = [{n}, {max_terms}], got {tuple(weights.shape)}")
+    if n < 1 or out.numel() != c * n * hw or (out.dim() == 5 and (out.shape[0] != 1 or out.shape[1] != c
+                                                                   or out.shape[2] != n)):
+        raise ValueError(f"overlap_blend: out must hold [C, F, hw] = [{c}, {n}, {hw}] values, got {tuple(out.shape)}")
+    # (hw % 4 == 0 and the 16-byte alignment of preds / out are the library's to check: a VxError before any launch)
+    L.check(_lib.vx_overlap_blend(_ptr(preds), c, f, hw, _ptr(terms), _ptr(weights), max_terms, n, _ptr(out), _stream()),
+            "vx_overlap_blend")
+
+
 def known_blend(latents, init, noise, mask, a, s):
     """Known-region blend of init-video sampling, in place: latents fp32 [1,C,F,h,w] <- m * latents + (1 - m) *
     (a * init + s * noise); init / noise fp32 shaped like latents, mask fp32 [F, h*w] in [0, 1] (1 = regenerate) shared

@@ -26,7 +26,7 @@ import torch
 
 from . import lib as L
 from . import ops
-from .context import get_context_scheduler, overlap_plan
+from .context import blend_weights, check_blend, get_context_scheduler, overlap_plan, weighted_overlap_plan
 from .distributed import (DistContext, MixedUnitSchedule, UnitSchedule, choose_frame_shards, choose_mixed_shards,
                           split_frames)
 from .mutual_self_attention import ReferenceAttentionControl
@@ -180,6 +180,11 @@ class VExpressPipeline:
         # loop started at, whether a latent mask was blended in after every step, and the vx_known_blend launches of the
         # call (the one that forms the start latents included; 0 without an init clip)
         self.last_init = {}
+        # the window stitch of the last denoise() call: dict(schedule, blend, windows, max_terms, blend_launches) - the
+        # context_schedule name (None when denoise was called directly: it takes the windows themselves), the blend
+        # ("mean", "linear", "pyramid" or "profile"), the number of windows, the most predictions summed into one frame
+        # and the vx_overlap_blend launches of the call (one per timestep of a weighted blend; 0 on the mean route)
+        self.last_overlap = {}
         # batch rows per UNet call: 2 = the two CFG halves of one window; 4 (default), 6, ... also merge consecutive
         # windows of this rank into one call.  Every kernel is batch-invariant, so the rows come out bit-identical;
         # merged calls measure 4-5 % faster (profiles/r02e_host_overhead.json: b = 3 74.0 ms vs 49.2 + 28.2 ms,
@@ -426,7 +431,7 @@ class VExpressPipeline:
     @_in_unet_element_type
     def denoise(self, latents, kps_tokens, audio, timesteps, windows, guidance_scale, callback=None,
                 callback_steps=1, *, begin_index=None, eta=0.0, noise_seed=None, guidance_rescale=0.0,
-                guidance_start=0.0, guidance_end=1.0, known=None, audio_guidance_scale=None):
+                guidance_start=0.0, guidance_end=1.0, known=None, audio_guidance_scale=None, overlap_blend="mean"):
         """pipelines/v_express_pipeline.py:526-583.  latents fp32 [1,4,F,h,w] (device, updated in place);
         kps_tokens bf16 [b, F, hw, C0]; audio bf16 [b, F, n_ctx, 768] with b = 2 (uncond, cond) under classifier-free
         guidance (guidance_scale > 1, :443) and b = 1 (the conditional row only) without.
@@ -451,8 +456,17 @@ class VExpressPipeline:
         at the level the latents now have, x = m x + (1 - m)(a_{i+1} init + s_{i+1} noise), and after the last of
         `timesteps` it is init itself, (a, s) = (1, 0), as in diffusers' inpaint loop (vx_known_blend; the same noise
         at every step; the multistep history and the ancestral noise are left alone; a callback sees the blended
-        latents).  m = None is plain img2img: no launch after the start."""
+        latents).  m = None is plain img2img: no launch after the start.
+        A weighted window blend (every sampler): overlap_blend = "linear", "pyramid" or a sequence of f positive weights
+        (context.blend_weights) replaces the 1 / count of the mean ("mean" or None: the reference's, :552-572) by
+        per-window, per-position weights normalised per frame.  One vx_overlap_blend launch per timestep, after the
+        combine / rescale launch (the rescale still acts per window), forms every frame's prediction; the sampler's
+        update then runs on that buffer with the trivial plan (one term, count 1), so x0 history, noise stream and the
+        known-region blend are what they are on the mean route.  The windows must not hold a frame twice ("linear":
+        contiguous runs by increasing start), which context_schedule="uniform_fit" gives for any clip length."""
         kind = self._sampler(eta)
+        blend_kind = check_blend(overlap_blend, len(windows[0]))
+        raw_weights = None if blend_kind == "mean" else blend_weights(windows, overlap_blend)
         guidance_rescale, guided = check_guidance(guidance_rescale, guidance_start, guidance_end, len(timesteps))
         row_names = guidance_rows(guidance_scale, audio_guidance_scale)
         init = noise = kmask = None
@@ -483,16 +497,30 @@ class VExpressPipeline:
         if any(len(w) != f for w in windows):
             raise ValueError("all context windows must have the same length")
         nW = len(windows)
-        plan = overlap_plan(windows, F)
         win_ids = torch.tensor(windows, dtype=torch.int32, device=dev)
-        sf = plan["step_frames"]
-        terms = torch.full((len(sf), plan["max_terms"], 2), -1, dtype=torch.int32)
-        for i, fr in enumerate(sf):
-            for j, (wi, li) in enumerate(plan["terms"][fr]):
-                terms[i, j, 0], terms[i, j, 1] = wi, li
-        terms = terms.to(dev)
-        frame_ids = torch.tensor(sf, dtype=torch.int32, device=dev)
-        counts = torch.tensor([float(plan["counts"][fr]) for fr in sf], dtype=torch.float32, device=dev)
+        blended = None
+        if raw_weights is None:
+            plan = overlap_plan(windows, F)
+            sf = plan["step_frames"]
+            terms = torch.full((len(sf), plan["max_terms"], 2), -1, dtype=torch.int32)
+            for i, fr in enumerate(sf):
+                for j, (wi, li) in enumerate(plan["terms"][fr]):
+                    terms[i, j, 0], terms[i, j, 1] = wi, li
+            terms = terms.to(dev)
+            frame_ids = torch.tensor(sf, dtype=torch.int32, device=dev)
+            counts = torch.tensor([float(plan["counts"][fr]) for fr in sf], dtype=torch.float32, device=dev)
+        else:
+            # the weighted blend is a pre-pass (identical on every rank, like the update): vx_overlap_blend forms every
+            # frame's prediction in `blended`, one "window" of F frames, and the update reads it through the trivial plan
+            plan = weighted_overlap_plan(windows, F, raw_weights)
+            blend_terms = torch.from_numpy(plan["term_table"]).to(dev)
+            blend_w = torch.from_numpy(plan["weights"]).to(dev)
+            blended = torch.empty((1, C, F, hw), device=dev, dtype=torch.float32)
+            frame_ids = torch.arange(F, dtype=torch.int32, device=dev)
+            terms = torch.stack([torch.zeros_like(frame_ids), frame_ids], dim=1).view(F, 1, 2).contiguous()
+            counts = torch.ones(F, dtype=torch.float32, device=dev)
+        self.last_overlap = dict(schedule=None, blend=blend_kind, windows=nW, max_terms=plan["max_terms"],
+                                 blend_launches=0 if blended is None else len(timesteps))
         do_cfg = len(row_names) > 1                   # a guided step combines rows
         three = len(row_names) == 3
         # the one scale of a two-row combine: (m, c) is guided by the audio scale
@@ -574,13 +602,18 @@ class VExpressPipeline:
                 # CFG combine of every window in one launch (:548-550; without CFG, and in an unguided step, the
                 # conditional prediction itself)
                 ops.combine_units(gathered, uidx, C, f, hw, scale2 if do_cfg and guided[i] else 1.0, preds)
+            step_preds = preds
+            if blended is not None:
+                ops.overlap_blend(preds, blend_terms, blend_w, blended)
+                step_preds = blended
             if multistep:
-                ops.overlap_multistep_step(latents, preds, terms, frame_ids, counts, x0_hist, coefs[i])
+                ops.overlap_multistep_step(latents, step_preds, terms, frame_ids, counts, x0_hist, coefs[i])
             elif ancestral:
-                ops.overlap_ancestral_step(latents, preds, terms, frame_ids, counts, coefs[i], noise_seed,
+                ops.overlap_ancestral_step(latents, step_preds, terms, frame_ids, counts, coefs[i], noise_seed,
                                            begin_index + i)
             else:
-                ops.overlap_ddim_step(latents, preds, terms, frame_ids, counts, self.scheduler.step_coefficients(t))
+                ops.overlap_ddim_step(latents, step_preds, terms, frame_ids, counts,
+                                      self.scheduler.step_coefficients(t))
             if blend is not None:
                 # the kept part again, at the level the latents have now (init itself after the last step)
                 ops.known_blend(latents, init, noise, kmask, *blend[i])
@@ -631,8 +664,14 @@ class VExpressPipeline:
                  reference_latents=None, kps_features=None, audio_embeddings=None, latents=None,
                  noise_seed: Optional[int] = None, output_device="cpu", decode=True, guidance_rescale: float = 0.0,
                  guidance_start: float = 0.0, guidance_end: float = 1.0, init_video=None, init_latents=None,
-                 mask=None, composite=True, audio_guidance_scale: Optional[float] = None, **kwargs):
-        """A separate audio scale: `audio_guidance_scale` = s_a (default None: the one scale of `guidance_scale` = s)
+                 mask=None, composite=True, audio_guidance_scale: Optional[float] = None, overlap_blend="mean",
+                 **kwargs):
+        """Window stitch: `context_schedule` = "uniform" (the reference's; a clip length that is not f + k (f - o) ends in
+        a reflected window with duplicate frames) or "uniform_fit" (the same number of windows spread evenly over any
+        length); `overlap_blend` = "mean" (default, also None: the reference's 1 / count) or a weighted blend of the
+        overlapping predictions - "linear" (a cross-fade over each actual overlap), "pyramid" or a sequence of
+        `context_frames` positive weights.  A weighted blend needs windows without duplicate frames: use "uniform_fit".
+        A separate audio scale: `audio_guidance_scale` = s_a (default None: the one scale of `guidance_scale` = s)
         guides on the audio apart from the reference image and the keypoints: u + s (m - u) + s_a (c - m), m the
         prediction with bank and keypoints but silent audio (three rows per window for s > 1 and s_a != s; the rows
         (m, c) for s <= 1 < s_a).  The prologue runs in the CFG layout whenever either scale exceeds 1.
@@ -648,6 +687,15 @@ class VExpressPipeline:
         kind = self._sampler(eta)
         check_guidance(guidance_rescale, guidance_start, guidance_end, max(int(num_inference_steps), 1))
         audio_guidance_scale = check_audio_guidance(audio_guidance_scale)
+        windows = None
+        if check_blend(overlap_blend, int(context_frames)) != "mean":
+            # a blend the schedule's windows cannot carry fails here too
+            windows = list(get_context_scheduler(context_schedule)(
+                step=0, num_frames=video_length, context_size=context_frames, context_stride=1,
+                context_overlap=context_overlap, closed_loop=False))
+            if not isinstance(overlap_blend, str):
+                overlap_blend = [float(v) for v in overlap_blend][:len(windows[0])]   # (one short window: F < f)
+            blend_weights(windows, overlap_blend)
         pixel_mask = check_init(init_video, init_latents, mask, video_length, height, width, self.vae_scale_factor,
                                 self.denoising_unet.in_channels)
         if init_video is not None and not hasattr(self.vae, "encode_video"):
@@ -681,9 +729,10 @@ class VExpressPipeline:
         if audio_embeddings is None:
             audio_embeddings = self.prepare_audio_embeddings(audio_waveform, video_length, num_pad_audio_frames,
                                                              do_cfg)
-        windows = list(get_context_scheduler(context_schedule)(
-            step=0, num_frames=video_length, context_size=context_frames, context_stride=1,
-            context_overlap=context_overlap, closed_loop=False))
+        if windows is None:
+            windows = list(get_context_scheduler(context_schedule)(
+                step=0, num_frames=video_length, context_size=context_frames, context_stride=1,
+                context_overlap=context_overlap, closed_loop=False))
         # ReferenceNet once per clip (:502-509)
         ehs0 = torch.zeros((1, 1, self.denoising_unet.cfg.cross_attention_dim), dtype=torch.float32, device=dev)
         self.reference_net(reference_latents.to(dev), timestep=0, encoder_hidden_states=ehs0, return_dict=False)
@@ -732,7 +781,8 @@ class VExpressPipeline:
         self.denoise(lat, kps_tokens, audio, timesteps, windows, guidance_scale, callback, callback_steps or 1,
                      begin_index=begin_index, eta=eta, noise_seed=noise_seed, guidance_rescale=guidance_rescale,
                      guidance_start=guidance_start, guidance_end=guidance_end, known=known,
-                     audio_guidance_scale=audio_guidance_scale)
+                     audio_guidance_scale=audio_guidance_scale, overlap_blend=overlap_blend)
+        self.last_overlap["schedule"] = context_schedule
         if timed:
             ev[1].record()
         reader.clear()
