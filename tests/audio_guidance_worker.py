@@ -7,12 +7,9 @@ import sys
 
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import cases  # noqa: E402
-import dist_gpu_worker as W  # noqa: E402
+import loop_worker as W  # noqa: E402  (first: it puts the repository on sys.path)
 import guidance_restated as G  # noqa: E402
 
 # name -> (F, context frames, overlap): one window = 3 units (on two ranks (u, m) | (c): the c row runs alone), two
@@ -24,33 +21,14 @@ S_AUDIO, STEPS, PHI, END = 6.0, 3, 0.7, 0.67
 
 def run(geometry, latent=8, device="cpu", frame_shards=1):
     """frame_shards = 1: whole units only, so that three units on two ranks leave one row alone on a rank."""
-    from v_express_amd import DDIMScheduler, ReferenceAttentionControl, ops, synth
-    from v_express_amd.context import get_context_scheduler
-    F, cf, co = GEOMETRY[geometry]
+    from v_express_amd import DDIMScheduler
     pipe = W.build_pipeline(device)
-    pipe.scheduler = sched = DDIMScheduler(**G.KWARGS)
+    pipe.scheduler = DDIMScheduler(**G.KWARGS)
     pipe.frame_shards = frame_shards
-    unet, refnet = pipe.denoising_unet, pipe.reference_net
-    cfg = cases.unet_cfg(cases.SMALL)
-    inp = synth.synthetic_inputs(cfg, F, latent, latent, device=device)
-    # the pieces of VExpressPipeline.__call__ in its order (as dist_gpu_worker._run on CPU tensors)
-    writer = ReferenceAttentionControl(refnet, do_classifier_free_guidance=True, mode="write", fusion_blocks="full")
-    reader = ReferenceAttentionControl(unet, do_classifier_free_guidance=True, mode="read", fusion_blocks="full",
-                                       reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD)
-    refnet(inp["ref_latents"], timestep=0, encoder_hidden_states=torch.zeros(1, 1, 768, device=device),
-           return_dict=False)
-    reader.update(writer, True, dtype=unet.dtype)
-    sched.set_timesteps(STEPS)
-    windows = list(get_context_scheduler("uniform")(step=0, num_frames=F, context_size=cf, context_stride=1,
-                                                    context_overlap=co, closed_loop=False))
-    c0 = cfg.block_out_channels[0]
-    kps = ops.ncfhw_to_nhwc(inp["kps_features"], c0).view(2, F, latent * latent, c0)
-    audio = inp["audio_embeddings"].to(torch.bfloat16).contiguous()
-    lat = inp["latents"].clone().float()
-    pipe.denoise(lat, kps, audio, sched.timesteps.tolist(), windows, cases.GUIDANCE, guidance_rescale=PHI,
-                 guidance_end=END, audio_guidance_scale=S_AUDIO)
+    lat = W.run_loop(pipe, *GEOMETRY[geometry], STEPS, latent=latent, device=device, guidance_rescale=PHI,
+                     guidance_end=END, audio_guidance_scale=S_AUDIO)
     assert pipe.last_guidance["guided_steps"] == 2 and pipe.last_guidance["rows"] == ("u", "m", "c")
-    return lat.cpu(), dict(pipe.last_schedule), dict(pipe.last_guidance)
+    return lat, dict(pipe.last_schedule), dict(pipe.last_guidance)
 
 
 def main(geometry, latent=8):

@@ -5,12 +5,9 @@ import sys
 
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import cases  # noqa: E402
-import dist_gpu_worker as W  # noqa: E402
+import loop_worker as W  # noqa: E402  (first: it puts the repository on sys.path)
 import dpm_restated as D  # noqa: E402
 
 # F = 14 in windows of 8 with overlap 2 (two windows, four CFG units), 3 DPM++ 2M steps (orders 1, 2, 1), 8x8 latents
@@ -21,8 +18,7 @@ def run():
     from v_express_amd import DPMSolverMultistepScheduler
     pipe = W.build_pipeline("cpu")
     pipe.scheduler = DPMSolverMultistepScheduler(**D.KWARGS)
-    return W._run(pipe, pipe.denoising_unet, pipe.reference_net, pipe.scheduler, cases.unet_cfg(cases.SMALL), F, CF,
-                  CO, STEPS, 0, LATENT, "cpu")
+    return W.run_loop(pipe, F, CF, CO, STEPS, latent=LATENT, device="cpu")
 
 
 def main():

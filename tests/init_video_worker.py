@@ -7,12 +7,10 @@ import sys
 
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import loop_worker as W  # noqa: E402  (first: it puts the repository on sys.path)
 import cases  # noqa: E402
-import dist_gpu_worker as W  # noqa: E402
 import init_video_restated as R  # noqa: E402
 
 # F = 14 in windows of 8 with overlap 2 (two windows, four CFG units), the last 3 of 5 DDIM steps

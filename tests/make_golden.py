@@ -274,10 +274,20 @@ def fullsize_768(out):
     print("fullsize_768", {k: (tuple(v.shape) if hasattr(v, "shape") else v) for k, v in g.items()})
 
 
+def loop_kernels(out):
+    """Digests of the float32 kernels of the denoising loop on the seeded inputs of tests/loop_kernels.py.  Unlike the rest
+    of this file it runs on an MI355X, with the library of the commit whose bits are to be kept (the parent of a change to
+    vx_elem.hip that must not alter them), and reads nothing of the reference."""
+    import loop_kernels as LK
+    LK.write(os.path.join(out, "loop_kernels_parent.json"))
+
+
 def main():
-    torch.set_num_threads(os.cpu_count())
     out = os.path.join(HERE, "golden")
     os.makedirs(out, exist_ok=True)
+    if len(sys.argv) > 1 and sys.argv[1] == "loop_kernels":  # on the GPU; not part of the default regeneration
+        return loop_kernels(out)
+    torch.set_num_threads(os.cpu_count())
     if len(sys.argv) > 1 and sys.argv[1] == "prologue":
         return prologue(out)
     if len(sys.argv) > 1 and sys.argv[1] == "wav2vec2":

@@ -104,41 +104,31 @@ __global__ void pack_rows_kernel(const float* __restrict__ src, int ld, long row
   dst[idx] = src[r * ld + ch];
 }
 
-// The all-gathered unit predictions [units_total, f_loc*hw, c] -> CFG-combined window predictions [nW, c, f, hw] in ONE
-// launch (replaces the per-slot copies + one cfg_combine per window).  unit_index: int32 [nW][halves][S] = index of the
-// unit buffer holding frame shard j of (window, CFG half).  halves == 1: the prediction itself (no guidance, :548-550
-// skipped: u + 1 * (u - u) is exactly u).
-__global__ void combine_units_kernel(const float* __restrict__ gathered, const int32_t* __restrict__ unit_index,
-                                     int n_windows, int halves, int shards, int c, int f, int f_loc, int hw,
-                                     float guidance, float* __restrict__ preds) {
-  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // (window, li, pixel)
-  long total = (long)n_windows * f * hw;
-  if (idx >= total) return;
-  int px = (int)(idx % hw);
-  int li = (int)((idx / hw) % f);
-  int wi = (int)(idx / ((long)hw * f));
-  int j = li / f_loc;
-  long row = (long)(li - j * f_loc) * hw + px;
-  long unit_sz = (long)f_loc * hw * c;
-  const float* u = gathered + unit_index[(wi * halves + 0) * shards + j] * unit_sz + row * c;
-  const float* cnd = halves > 1 ? gathered + unit_index[(wi * halves + 1) * shards + j] * unit_sz + row * c : u;
-  for (int ch = 0; ch < c; ++ch)
-    preds[(((size_t)wi * c + ch) * f + li) * hw + px] = u[ch] + guidance * (cnd[ch] - u[ch]);
-}
-
-// Three-row guidance (a separate audio scale): unit_index int32 [nW][3][S] names the rows (u, m, c) of a window - u without
-// any condition, m ("silent") with the reference bank and the keypoints but all-zero audio, c with everything - and the
-// prediction is g = u + s (m - u) + s_audio (c - m), evaluated as cfg_mix(u, m, s) + s_audio * (c - m): where c and m hold
-// equal bits this is the two-row kernel's u + s (m - u).
+// g = u + s (cnd - u), and for three-row guidance (a separate audio scale) g = u + s (m - u) + s_audio (c - m) over the rows
+// (u, m, c) of a window - u without any condition, m ("silent") with the reference bank and the keypoints but all-zero audio,
+// c with everything - evaluated as cfg_mix(u, m, s) + s_audio * (c - m): where c and m hold equal bits this is the two-row
+// u + s (m - u).
 __device__ __forceinline__ float cfg_mix(float u, float cnd, float guidance) { return u + guidance * (cnd - u); }
 
 __device__ __forceinline__ float cfg_mix3(float u, float m, float cnd, float guidance, float audio) {
   return cfg_mix(u, m, guidance) + audio * (cnd - m);
 }
 
-__global__ void combine_units3_kernel(const float* __restrict__ gathered, const int32_t* __restrict__ unit_index,
-                                      int n_windows, int shards, int c, int f, int f_loc, int hw, float guidance,
-                                      float audio, float* __restrict__ preds) {
+// the guided prediction at one element of a window's rows: rows[0] = u, rows[ROWS - 1] = c, and rows[1] = m for ROWS = 3.
+// ROWS = 1 (no guidance) evaluates u + s (u - u) like the others: -0.0 comes out as +0.0 and an infinity as NaN
+template <int ROWS>
+__device__ __forceinline__ float guided_value(const float* const* rows, long i, float guidance, float audio) {
+  if constexpr (ROWS == 3) return cfg_mix3(rows[0][i], rows[1][i], rows[2][i], guidance, audio);
+  else return cfg_mix(rows[0][i], rows[ROWS - 1][i], guidance);
+}
+
+// The all-gathered unit predictions [units_total, f_loc*hw, c] -> guided window predictions [nW, c, f, hw] in ONE launch
+// (replaces the per-slot copies + one cfg_combine per window).  unit_index: int32 [nW][ROWS][S] = index of the unit buffer
+// holding frame shard j of (window, row).
+template <int ROWS>
+__global__ void combine_units_kernel(const float* __restrict__ gathered, const int32_t* __restrict__ unit_index,
+                                     int n_windows, int shards, int c, int f, int f_loc, int hw, float guidance,
+                                     float audio, float* __restrict__ preds) {
   long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // (window, li, pixel)
   long total = (long)n_windows * f * hw;
   if (idx >= total) return;
@@ -148,11 +138,11 @@ __global__ void combine_units3_kernel(const float* __restrict__ gathered, const 
   int j = li / f_loc;
   long row = (long)(li - j * f_loc) * hw + px;
   long unit_sz = (long)f_loc * hw * c;
-  const float* u = gathered + unit_index[(wi * 3 + 0) * shards + j] * unit_sz + row * c;
-  const float* m = gathered + unit_index[(wi * 3 + 1) * shards + j] * unit_sz + row * c;
-  const float* cnd = gathered + unit_index[(wi * 3 + 2) * shards + j] * unit_sz + row * c;
+  const float* rows[ROWS];
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r) rows[r] = gathered + unit_index[(wi * ROWS + r) * shards + j] * unit_sz + row * c;
   for (int ch = 0; ch < c; ++ch)
-    preds[(((size_t)wi * c + ch) * f + li) * hw + px] = cfg_mix3(u[ch], m[ch], cnd[ch], guidance, audio);
+    preds[(((size_t)wi * c + ch) * f + li) * hw + px] = guided_value<ROWS>(rows, ch, guidance, audio);
 }
 
 // CFG rescale (Lin et al. 2024, diffusers rescale_noise_cfg): per window, g = u + s (c - u) scaled by
@@ -188,13 +178,6 @@ __device__ __forceinline__ void block_sum2(float& a, float& b, float* lds) {
     a += lds[2 * w];
     b += lds[2 * w + 1];
   }
-}
-
-// the guided prediction at one element of a window's rows: rows[0] = u, rows[ROWS - 1] = c, and rows[1] = m for ROWS = 3
-template <int ROWS>
-__device__ __forceinline__ float guided_value(const float* const* rows, long i, float guidance, float audio) {
-  if constexpr (ROWS == 2) return cfg_mix(rows[0][i], rows[1][i], guidance);
-  else return cfg_mix3(rows[0][i], rows[1][i], rows[2][i], guidance, audio);
 }
 
 template <int ROWS>
@@ -286,6 +269,44 @@ __global__ __launch_bounds__(GR_THREADS) void guidance_scale_kernel(const float*
     preds[(((size_t)wi * c + ch) * f + li) * hw + px] = guided_value<ROWS>(rows, ch, guidance, audio) * factor;
 }
 
+// The mean of the overlapping predictions of frame slot fs at (ch, px): the reference divides each window's prediction by
+// the coverage count BEFORE summing (:553, :556-564); the first valid term initialises the sum, slot < 0 = skip.  The float4
+// form is the same per component (px = the first pixel of the quad, 16-byte aligned rows).
+__device__ __forceinline__ float mean_of_terms(const float* preds, int c, int f_window, int hw, const int32_t* terms,
+                                               int max_terms, int fs, int ch, int px, float ic) {
+  float v = 0.f;
+  bool first = true;
+  for (int t = 0; t < max_terms; ++t) {
+    int slot = terms[(fs * max_terms + t) * 2 + 0];
+    int li = terms[(fs * max_terms + t) * 2 + 1];
+    if (slot < 0) continue;
+    float term = preds[(((size_t)slot * c + ch) * f_window + li) * hw + px] / ic;
+    v = first ? term : v + term;
+    first = false;
+  }
+  return v;
+}
+
+__device__ __forceinline__ float4 mean_of_terms4(const float* preds, int c, int f_window, int hw, const int32_t* terms,
+                                                 int max_terms, int fs, int ch, int px, float ic) {
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  bool first = true;
+  for (int t = 0; t < max_terms; ++t) {
+    int slot = terms[(fs * max_terms + t) * 2 + 0];
+    int li = terms[(fs * max_terms + t) * 2 + 1];
+    if (slot < 0) continue;
+    const float4 p = *reinterpret_cast<const float4*>(preds + (((size_t)slot * c + ch) * f_window + li) * hw + px);
+    const float4 term = make_float4(p.x / ic, p.y / ic, p.z / ic, p.w / ic);
+    if (first) {
+      v = term;
+    } else {
+      v.x = v.x + term.x; v.y = v.y + term.y; v.z = v.z + term.z; v.w = v.w + term.w;
+    }
+    first = false;
+  }
+  return v;
+}
+
 __global__ void overlap_ddim_kernel(float* latents, int c, int total_frames, int hw, const float* preds, int f_window,
                                     const int32_t* terms, int max_terms, const int32_t* frame_ids,
                                     const float* count, int n_frames, float sqrt_a, float sqrt_1ma,
@@ -297,18 +318,7 @@ __global__ void overlap_ddim_kernel(float* latents, int c, int total_frames, int
   int ch = (int)((idx / hw) % c);
   int fs = (int)(idx / ((long)hw * c));
   int fr = frame_ids[fs];
-  float ic = count[fs];
-  float v = 0.f;
-  bool first = true;
-  for (int t = 0; t < max_terms; ++t) {
-    int slot = terms[(fs * max_terms + t) * 2 + 0];
-    int li = terms[(fs * max_terms + t) * 2 + 1];
-    if (slot < 0) continue;
-    // the reference divides each window's prediction by the coverage count BEFORE summing (:553, :556-564)
-    float term = preds[(((size_t)slot * c + ch) * f_window + li) * hw + px] / ic;
-    v = first ? term : v + term;
-    first = false;
-  }
+  float v = mean_of_terms(preds, c, f_window, hw, terms, max_terms, fs, ch, px, count[fs]);
   float* lp = latents + ((size_t)ch * total_frames + fr) * hw + px;
   float x = *lp;
   float x0 = sqrt_a * x - sqrt_1ma * v;
@@ -331,17 +341,7 @@ __global__ void overlap_multistep_kernel(float* latents, int c, int total_frames
   int ch = (int)((idx / hw) % c);
   int fs = (int)(idx / ((long)hw * c));
   int fr = frame_ids[fs];
-  float ic = count[fs];
-  float v = 0.f;
-  bool first = true;
-  for (int t = 0; t < max_terms; ++t) {
-    int slot = terms[(fs * max_terms + t) * 2 + 0];
-    int li = terms[(fs * max_terms + t) * 2 + 1];
-    if (slot < 0) continue;
-    float term = preds[(((size_t)slot * c + ch) * f_window + li) * hw + px] / ic;
-    v = first ? term : v + term;
-    first = false;
-  }
+  float v = mean_of_terms(preds, c, f_window, hw, terms, max_terms, fs, ch, px, count[fs]);
   size_t off = ((size_t)ch * total_frames + fr) * hw + px;
   float x = latents[off];
   float x0 = alpha_s * x - sigma_s * v;
@@ -367,22 +367,7 @@ __global__ void overlap_ancestral_kernel(float* latents, int c, int total_frames
   int ch = (int)((idx / hq) % c);
   int fs = (int)(idx / ((long)hq * c));
   int fr = frame_ids[fs];
-  float ic = count[fs];
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  bool first = true;
-  for (int t = 0; t < max_terms; ++t) {
-    int slot = terms[(fs * max_terms + t) * 2 + 0];
-    int li = terms[(fs * max_terms + t) * 2 + 1];
-    if (slot < 0) continue;
-    const float4 p = *reinterpret_cast<const float4*>(preds + (((size_t)slot * c + ch) * f_window + li) * hw + 4 * q);
-    const float4 term = make_float4(p.x / ic, p.y / ic, p.z / ic, p.w / ic);
-    if (first) {
-      v = term;
-    } else {
-      v.x = v.x + term.x; v.y = v.y + term.y; v.z = v.z + term.z; v.w = v.w + term.w;
-    }
-    first = false;
-  }
+  const float4 v = mean_of_terms4(preds, c, f_window, hw, terms, max_terms, fs, ch, 4 * q, count[fs]);
   float4* lp = reinterpret_cast<float4*>(latents + ((size_t)ch * total_frames + fr) * hw + 4 * q);
   const float4 x = *lp;
   float4 out;
@@ -668,8 +653,12 @@ extern "C" int vx_combine_units(const float* gathered, const int32_t* unit_index
   VX_REQUIRE(gathered && unit_index && preds && n_windows > 0 && (halves == 1 || halves == 2) && shards > 0 && c > 0 &&
                  f > 0 && hw > 0 && f % shards == 0,
              "vx_combine_units: bad arguments");
-  hipLaunchKernelGGL(combine_units_kernel, grid1d((long)n_windows * f * hw), dim3(256), 0, (hipStream_t)stream,
-                     gathered, unit_index, n_windows, halves, shards, c, f, f / shards, hw, guidance, preds);
+  if (halves == 1)
+    hipLaunchKernelGGL(combine_units_kernel<1>, grid1d((long)n_windows * f * hw), dim3(256), 0, (hipStream_t)stream,
+                       gathered, unit_index, n_windows, shards, c, f, f / shards, hw, guidance, 0.f, preds);
+  else
+    hipLaunchKernelGGL(combine_units_kernel<2>, grid1d((long)n_windows * f * hw), dim3(256), 0, (hipStream_t)stream,
+                       gathered, unit_index, n_windows, shards, c, f, f / shards, hw, guidance, 0.f, preds);
   return vx_check_launch("vx_combine_units");
 }
 
@@ -678,11 +667,20 @@ extern "C" int64_t vx_guidance_rescale_ws_floats(int n_windows, int f, int hw) {
   return (int64_t)n_windows * f * ((hw + GR_CHUNK - 1) / GR_CHUNK) * 6;
 }
 
-// the two launches of vx_guidance_rescale (ROWS = 2) / vx_guidance_rescale3 (ROWS = 3), arguments already validated
+// the argument checks and the two launches of vx_guidance_rescale (ROWS = 2) / vx_guidance_rescale3 (ROWS = 3)
 template <int ROWS>
 static int launch_guidance_rescale(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c,
                                    int f, int hw, float guidance, float audio, float phi, float* workspace,
-                                   float* preds, void* stream, const char* stats_name, const char* name) {
+                                   int64_t ws_floats, float* preds, void* stream, const char* stats_name,
+                                   const char* name) {
+  VX_REQUIRE(gathered && unit_index && workspace && preds && n_windows > 0 && n_windows <= 65535 && shards > 0 && c > 0 &&
+                 f > 0 && hw > 0 && f % shards == 0,
+             "%s: bad arguments", name);
+  VX_REQUIRE(phi >= 0.f && phi <= 1.f, "%s: phi must lie in [0, 1]", name);
+  VX_REQUIRE((long)c * f * hw >= 2, "%s: the standard deviation needs two values per window", name);
+  VX_REQUIRE(ws_floats >= vx_guidance_rescale_ws_floats(n_windows, f, hw),
+             "%s: workspace too small (vx_guidance_rescale_ws_floats)", name);
+  VX_REQUIRE((long)n_windows * f * ((hw + GR_CHUNK - 1) / GR_CHUNK) <= 0x7fffffffL, "%s: too many partials", name);
   const int chunks = (hw + GR_CHUNK - 1) / GR_CHUNK;
   if (phi != 0.f) {
     hipLaunchKernelGGL(guidance_stats_kernel<ROWS>, dim3((unsigned)(n_windows * f * chunks)), dim3(GR_THREADS), 0,
@@ -701,17 +699,8 @@ static int launch_guidance_rescale(const float* gathered, const int32_t* unit_in
 extern "C" int vx_guidance_rescale(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c,
                                    int f, int hw, float guidance, float phi, float* workspace, int64_t ws_floats,
                                    float* preds, void* stream) {
-  VX_REQUIRE(gathered && unit_index && workspace && preds && n_windows > 0 && n_windows <= 65535 && shards > 0 && c > 0 &&
-                 f > 0 && hw > 0 && f % shards == 0,
-             "vx_guidance_rescale: bad arguments");
-  VX_REQUIRE(phi >= 0.f && phi <= 1.f, "vx_guidance_rescale: phi must lie in [0, 1]");
-  VX_REQUIRE((long)c * f * hw >= 2, "vx_guidance_rescale: the standard deviation needs two values per window");
-  VX_REQUIRE(ws_floats >= vx_guidance_rescale_ws_floats(n_windows, f, hw),
-             "vx_guidance_rescale: workspace too small (vx_guidance_rescale_ws_floats)");
-  VX_REQUIRE((long)n_windows * f * ((hw + GR_CHUNK - 1) / GR_CHUNK) <= 0x7fffffffL,
-             "vx_guidance_rescale: too many partials");
   return launch_guidance_rescale<2>(gathered, unit_index, n_windows, shards, c, f, hw, guidance, 0.f, phi, workspace,
-                                    preds, stream, "vx_guidance_rescale (statistics)", "vx_guidance_rescale");
+                                    ws_floats, preds, stream, "vx_guidance_rescale (statistics)", "vx_guidance_rescale");
 }
 
 extern "C" int vx_combine_units3(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c,
@@ -719,7 +708,7 @@ extern "C" int vx_combine_units3(const float* gathered, const int32_t* unit_inde
   VX_REQUIRE(gathered && unit_index && preds && n_windows > 0 && shards > 0 && c > 0 && f > 0 && hw > 0 &&
                  f % shards == 0,
              "vx_combine_units3: bad arguments");
-  hipLaunchKernelGGL(combine_units3_kernel, grid1d((long)n_windows * f * hw), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(combine_units_kernel<3>, grid1d((long)n_windows * f * hw), dim3(256), 0, (hipStream_t)stream,
                      gathered, unit_index, n_windows, shards, c, f, f / shards, hw, guidance, audio_guidance, preds);
   return vx_check_launch("vx_combine_units3");
 }
@@ -727,17 +716,8 @@ extern "C" int vx_combine_units3(const float* gathered, const int32_t* unit_inde
 extern "C" int vx_guidance_rescale3(const float* gathered, const int32_t* unit_index, int n_windows, int shards, int c,
                                     int f, int hw, float guidance, float audio_guidance, float phi, float* workspace,
                                     int64_t ws_floats, float* preds, void* stream) {
-  VX_REQUIRE(gathered && unit_index && workspace && preds && n_windows > 0 && n_windows <= 65535 && shards > 0 && c > 0 &&
-                 f > 0 && hw > 0 && f % shards == 0,
-             "vx_guidance_rescale3: bad arguments");
-  VX_REQUIRE(phi >= 0.f && phi <= 1.f, "vx_guidance_rescale3: phi must lie in [0, 1]");
-  VX_REQUIRE((long)c * f * hw >= 2, "vx_guidance_rescale3: the standard deviation needs two values per window");
-  VX_REQUIRE(ws_floats >= vx_guidance_rescale_ws_floats(n_windows, f, hw),
-             "vx_guidance_rescale3: workspace too small (vx_guidance_rescale_ws_floats)");
-  VX_REQUIRE((long)n_windows * f * ((hw + GR_CHUNK - 1) / GR_CHUNK) <= 0x7fffffffL,
-             "vx_guidance_rescale3: too many partials");
   return launch_guidance_rescale<3>(gathered, unit_index, n_windows, shards, c, f, hw, guidance, audio_guidance, phi,
-                                    workspace, preds, stream, "vx_guidance_rescale3 (statistics)",
+                                    workspace, ws_floats, preds, stream, "vx_guidance_rescale3 (statistics)",
                                     "vx_guidance_rescale3");
 }
 

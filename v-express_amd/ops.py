@@ -1338,47 +1338,50 @@ def guidance_rescale_ws_floats(nW, f, hw):
     return int(_lib.vx_guidance_rescale_ws_floats(int(nW), int(f), int(hw)))
 
 
+# what the [nW, rows, S] unit index of a guided combine names, for its error message
+_UNIT_ROWS = {2: "both CFG halves", 3: "the rows u, m, c of every window"}
+
+
+def _check_units(name, rows, gathered, unit_index, c, f, hw, preds, workspace=None, phi=None, ws_with_buffers=False):
+    """The host checks of `guidance_rescale` (rows = 2), `combine_units3` and `guidance_rescale3` (rows = 3); the rescales
+    pass workspace and phi.  Returns (nW, S).  ws_with_buffers (`guidance_rescale`, which needs a workspace): a bad
+    workspace is reported together with gathered / preds, before the size check, as that op always has."""
+    if unit_index.dim() != 3 or unit_index.shape[1] != rows:
+        raise ValueError(f"{name}: unit_index must be [nW, {rows}, S] ({_UNIT_ROWS[rows]})")
+    nW, _, S = unit_index.shape
+    if unit_index.dtype != torch.int32 or not unit_index.is_contiguous() or not gathered.is_contiguous():
+        raise TypeError(f"{name}: contiguous int32 index / contiguous gathered buffer expected")
+    buffers = [preds, workspace] if ws_with_buffers else [preds]
+    if gathered.dtype != torch.float32 or any(t.dtype != torch.float32 or not t.is_contiguous() for t in buffers):
+        raise TypeError(f"{name}: contiguous float32 gathered / {'workspace / ' if ws_with_buffers else ''}preds expected")
+    if f % S or gathered.numel() % ((f // S) * hw * c) or preds.numel() != nW * c * f * hw:
+        raise ValueError(f"{name}: buffer sizes do not match (nW, c, f, hw, S)")
+    if workspace is not None:
+        if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+            raise TypeError(f"{name}: contiguous float32 workspace expected")
+        if not 0.0 <= float(phi) <= 1.0:
+            raise ValueError(f"{name}: phi must lie in [0, 1], got {phi}")
+        if workspace.numel() < guidance_rescale_ws_floats(nW, f, hw):
+            raise ValueError(f"{name}: workspace smaller than guidance_rescale_ws_floats(nW, f, hw)")
+    return nW, S
+
+
 def guidance_rescale(gathered, unit_index, c, f, hw, guidance, phi, workspace, preds):
     """`combine_units` with the CFG rescale of diffusers' rescale_noise_cfg: gathered fp32 [units_total, (f/S)*hw, c],
     unit_index int32 [nW, 2, S] -> preds fp32 [nW, c, f, hw] = g * (1 + phi (std(cond) / std(g) - 1)) per window,
     g = u + guidance (cond - u); workspace: float32, at least guidance_rescale_ws_floats(nW, f, hw) elements."""
-    if unit_index.dim() != 3 or unit_index.shape[1] != 2:
-        raise ValueError("guidance_rescale: unit_index must be [nW, 2, S] (both CFG halves)")
-    nW, _, S = unit_index.shape
-    if unit_index.dtype != torch.int32 or not unit_index.is_contiguous() or not gathered.is_contiguous():
-        raise TypeError("guidance_rescale: contiguous int32 index / contiguous gathered buffer expected")
-    if (gathered.dtype != torch.float32 or preds.dtype != torch.float32 or workspace.dtype != torch.float32
-            or not preds.is_contiguous() or not workspace.is_contiguous()):
-        raise TypeError("guidance_rescale: contiguous float32 gathered / workspace / preds expected")
-    if f % S or gathered.numel() % ((f // S) * hw * c) or preds.numel() != nW * c * f * hw:
-        raise ValueError("guidance_rescale: buffer sizes do not match (nW, c, f, hw, S)")
-    if not 0.0 <= float(phi) <= 1.0:
-        raise ValueError(f"guidance_rescale: phi must lie in [0, 1], got {phi}")
-    if workspace.numel() < guidance_rescale_ws_floats(nW, f, hw):
-        raise ValueError("guidance_rescale: workspace smaller than guidance_rescale_ws_floats(nW, f, hw)")
+    nW, S = _check_units("guidance_rescale", 2, gathered, unit_index, c, f, hw, preds, workspace, phi,
+                         ws_with_buffers=True)
     L.check(_lib.vx_guidance_rescale(_ptr(gathered), _ptr(unit_index), nW, S, c, f, hw, float(guidance), float(phi),
                                      _ptr(workspace), workspace.numel(), _ptr(preds), _stream()),
             "vx_guidance_rescale")
-
-
-def _check_units3(name, gathered, unit_index, c, f, hw, preds):
-    if unit_index.dim() != 3 or unit_index.shape[1] != 3:
-        raise ValueError(f"{name}: unit_index must be [nW, 3, S] (the rows u, m, c of every window)")
-    nW, _, S = unit_index.shape
-    if unit_index.dtype != torch.int32 or not unit_index.is_contiguous() or not gathered.is_contiguous():
-        raise TypeError(f"{name}: contiguous int32 index / contiguous gathered buffer expected")
-    if gathered.dtype != torch.float32 or preds.dtype != torch.float32 or not preds.is_contiguous():
-        raise TypeError(f"{name}: contiguous float32 gathered / preds expected")
-    if f % S or gathered.numel() % ((f // S) * hw * c) or preds.numel() != nW * c * f * hw:
-        raise ValueError(f"{name}: buffer sizes do not match (nW, c, f, hw, S)")
-    return nW, S
 
 
 def combine_units3(gathered, unit_index, c, f, hw, guidance, audio_guidance, preds):
     """`combine_units` for three-row guidance: gathered fp32 [units_total, (f/S)*hw, c]; unit_index int32 [nW, 3, S] naming
     the rows (u, m, c) of every window (m: reference + keypoints, zero audio) -> preds fp32 [nW, c, f, hw] =
     u + guidance (m - u) + audio_guidance (c - m)."""
-    nW, S = _check_units3("combine_units3", gathered, unit_index, c, f, hw, preds)
+    nW, S = _check_units("combine_units3", 3, gathered, unit_index, c, f, hw, preds)
     L.check(_lib.vx_combine_units3(_ptr(gathered), _ptr(unit_index), nW, S, c, f, hw, float(guidance),
                                    float(audio_guidance), _ptr(preds), _stream()), "vx_combine_units3")
 
@@ -1387,13 +1390,7 @@ def guidance_rescale3(gathered, unit_index, c, f, hw, guidance, audio_guidance, 
     """`guidance_rescale` for three-row guidance: preds = g * (1 + phi (std(c) / std(g) - 1)) per window with
     g = u + guidance (m - u) + audio_guidance (c - m) and c the fully conditional row; workspace as `guidance_rescale`
     takes it (guidance_rescale_ws_floats(nW, f, hw) float32 elements)."""
-    nW, S = _check_units3("guidance_rescale3", gathered, unit_index, c, f, hw, preds)
-    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
-        raise TypeError("guidance_rescale3: contiguous float32 workspace expected")
-    if not 0.0 <= float(phi) <= 1.0:
-        raise ValueError(f"guidance_rescale3: phi must lie in [0, 1], got {phi}")
-    if workspace.numel() < guidance_rescale_ws_floats(nW, f, hw):
-        raise ValueError("guidance_rescale3: workspace smaller than guidance_rescale_ws_floats(nW, f, hw)")
+    nW, S = _check_units("guidance_rescale3", 3, gathered, unit_index, c, f, hw, preds, workspace, phi)
     L.check(_lib.vx_guidance_rescale3(_ptr(gathered), _ptr(unit_index), nW, S, c, f, hw, float(guidance),
                                       float(audio_guidance), float(phi), _ptr(workspace), workspace.numel(),
                                       _ptr(preds), _stream()), "vx_guidance_rescale3")

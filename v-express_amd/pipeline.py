@@ -30,6 +30,8 @@ from .context import blend_weights, check_blend, get_context_scheduler, overlap_
 from .distributed import (DistContext, MixedUnitSchedule, UnitSchedule, choose_frame_shards, choose_mixed_shards,
                           split_frames)
 from .mutual_self_attention import ReferenceAttentionControl
+from .sampling import (ANCESTRAL, GUIDANCE_ROWS, Guidance, Known, Sampler, Stitch, UnitCall, ancestral_coefficients,
+                       check_known)
 from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
 
 
@@ -71,12 +73,6 @@ def check_guidance(guidance_rescale, guidance_start, guidance_end, n):
     if start > end:
         raise ValueError(f"guidance_start ({guidance_start}) must not exceed guidance_end ({guidance_end})")
     return phi, guided_steps(n, start, end)
-
-
-# The batch rows a window can run, as (bank row, keypoint row, audio row) of the CFG-layout conditioning (row 0 zeros,
-# row 1 real): "u" drops everything, "m" ("silent") keeps the reference bank and the keypoints and drops the audio, "c"
-# keeps everything.
-GUIDANCE_ROWS = {"u": (0, 0, 0), "m": (1, 1, 0), "c": (1, 1, 1)}
 
 
 def check_audio_guidance(audio_guidance_scale):
@@ -324,12 +320,6 @@ class VExpressPipeline:
                         f"v_express_amd.DPMSolverMultistepScheduler or v_express_amd.EulerAncestralDiscreteScheduler, "
                         f"not {type(self.scheduler).__name__}")
 
-    def _ancestral_coefficients(self, kind, timesteps, begin_index, eta):
-        """Per-step (alpha_s, sigma_s, c_x, c_0, c_z) of an ancestral sampler, resolved on the host before the loop."""
-        if kind == "ddim-eta":
-            return [self.scheduler.ancestral_coefficients(t, eta) for t in timesteps]
-        return [self.scheduler.ancestral_coefficients(begin_index + i) for i in range(len(timesteps))]
-
     def _unit_plan(self, latents, kps_tokens, audio, audio_is_zero, windows, win_ids, half_rows):
         """The static plan of one kind of timestep: which (window, half) units this rank computes, in which UNet calls,
         and where they land in the exchange buffer.  `half_rows`: the row of the kps / audio tensors and of the reference
@@ -337,7 +327,7 @@ class VExpressPipeline:
         conditional half alone of a CFG clip (an unguided step).  An entry may also name the three separately, as
         (bank row, keypoint row, audio row): GUIDANCE_ROWS["m"] = (1, 1, 0) is the silent row of three-row guidance (an
         int r stands for (r, r, r)).  Collective (`dc.frame_shard`): every rank builds it.
-        Returns dict(calls, local, uidx, max_slots, schedule)."""
+        Returns dict(calls, local, uidx, max_slots, schedule), calls a list of sampling.UnitCall."""
         unet, dc, dev = self.denoising_unet, self.dist, latents.device
         _, C, F, H, W = latents.shape
         hw = H * W
@@ -424,8 +414,8 @@ class VExpressPipeline:
                 n_slots = len(rows) * (G // Sc)
                 # the audio K | V of all 16 transformer blocks is step-invariant: once per clip and call
                 bank_rows = [row_of[hlf][0] for _, hlf in rows]
-                calls.append((bank_rows, gathers, kps, ehs, unet.precompute_audio_kv(ehs),
-                              [audio_is_zero[row_of[hlf][2]] for _, hlf in rows], f_loc, shard, s0, n_slots))
+                calls.append(UnitCall(bank_rows, gathers, kps, ehs, unet.precompute_audio_kv(ehs),
+                                      [audio_is_zero[row_of[hlf][2]] for _, hlf in rows], f_loc, shard, s0, n_slots))
         return dict(calls=calls, local=local, uidx=uidx, max_slots=max_slots, schedule=schedule)
 
     @_in_unet_element_type
@@ -469,16 +459,7 @@ class VExpressPipeline:
         raw_weights = None if blend_kind == "mean" else blend_weights(windows, overlap_blend)
         guidance_rescale, guided = check_guidance(guidance_rescale, guidance_start, guidance_end, len(timesteps))
         row_names = guidance_rows(guidance_scale, audio_guidance_scale)
-        init = noise = kmask = None
-        if known is not None:
-            init, noise, kmask = known
-            for t, name in ((init, "init"), (noise, "noise")):
-                if tuple(t.shape) != tuple(latents.shape):
-                    raise ValueError(f"known: {name} must be shaped like the latents {tuple(latents.shape)}, got "
-                                     f"{tuple(t.shape)}")
-            want = (latents.shape[2], latents.shape[3] * latents.shape[4])
-            if kmask is not None and tuple(kmask.shape) != want:
-                raise ValueError(f"known: the latent mask must be [F, h * w] = {list(want)}, got {tuple(kmask.shape)}")
+        init, noise, kmask = check_known(known, latents)
         if kind != "ddim" or known is not None:
             all_ts = [int(t) for t in self.scheduler.timesteps.tolist()]
             if begin_index is None:
@@ -486,10 +467,8 @@ class VExpressPipeline:
             if [int(t) for t in timesteps] != all_ts[begin_index:begin_index + len(timesteps)]:
                 raise ValueError(f"{type(self.scheduler).__name__}: timesteps must be the scheduler's own, from step "
                                  f"index begin_index on")
-        ancestral = kind in ("ddim-eta", "euler-a")
-        if ancestral and noise_seed is None:
+        if kind in ANCESTRAL and noise_seed is None:
             raise ValueError(f"the {kind} sampler draws noise on the device: pass noise_seed")
-        multistep = kind == "dpm"
         unet, dc, dev = self.denoising_unet, self.dist, latents.device
         _, C, F, H, W = latents.shape
         hw = H * W
@@ -498,132 +477,43 @@ class VExpressPipeline:
             raise ValueError("all context windows must have the same length")
         nW = len(windows)
         win_ids = torch.tensor(windows, dtype=torch.int32, device=dev)
-        blended = None
-        if raw_weights is None:
-            plan = overlap_plan(windows, F)
-            sf = plan["step_frames"]
-            terms = torch.full((len(sf), plan["max_terms"], 2), -1, dtype=torch.int32)
-            for i, fr in enumerate(sf):
-                for j, (wi, li) in enumerate(plan["terms"][fr]):
-                    terms[i, j, 0], terms[i, j, 1] = wi, li
-            terms = terms.to(dev)
-            frame_ids = torch.tensor(sf, dtype=torch.int32, device=dev)
-            counts = torch.tensor([float(plan["counts"][fr]) for fr in sf], dtype=torch.float32, device=dev)
-        else:
-            # the weighted blend is a pre-pass (identical on every rank, like the update): vx_overlap_blend forms every
-            # frame's prediction in `blended`, one "window" of F frames, and the update reads it through the trivial plan
-            plan = weighted_overlap_plan(windows, F, raw_weights)
-            blend_terms = torch.from_numpy(plan["term_table"]).to(dev)
-            blend_w = torch.from_numpy(plan["weights"]).to(dev)
-            blended = torch.empty((1, C, F, hw), device=dev, dtype=torch.float32)
-            frame_ids = torch.arange(F, dtype=torch.int32, device=dev)
-            terms = torch.stack([torch.zeros_like(frame_ids), frame_ids], dim=1).view(F, 1, 2).contiguous()
-            counts = torch.ones(F, dtype=torch.float32, device=dev)
-        self.last_overlap = dict(schedule=None, blend=blend_kind, windows=nW, max_terms=plan["max_terms"],
-                                 blend_launches=0 if blended is None else len(timesteps))
-        do_cfg = len(row_names) > 1                   # a guided step combines rows
-        three = len(row_names) == 3
-        # the one scale of a two-row combine: (m, c) is guided by the audio scale
-        scale2 = float(audio_guidance_scale) if row_names == ("m", "c") else guidance_scale
-        cond_rows = 2 if do_cfg else 1
-        if kps_tokens.shape[0] != cond_rows or audio.shape[0] != cond_rows:
-            what = f"guidance_scale={guidance_scale}"
-            if row_names in (("m", "c"), ("u", "m", "c")):
-                what += f" with audio_guidance_scale={audio_guidance_scale} (the silent row takes the zero-audio row 0)"
-            raise ValueError(f"{what} needs {cond_rows} batch row(s) of kps features / audio embeddings, got "
-                             f"{kps_tokens.shape[0]} / {audio.shape[0]}")
-        if not do_cfg:                                # nothing to rescale, nothing to switch off
-            guidance_rescale, guided = 0.0, [True] * len(timesteps)
-        # which CFG halves carry all-zero audio tokens (the unconditional half, :403-405): one device reduction per clip
-        audio_is_zero = [bool((audio[hh] == 0).all().item()) for hh in range(audio.shape[0])]
-        # one plan for the guided steps (every step, by default); a second one, the conditional half alone, only when
-        # some step runs without guidance.  Both are built on every rank, before the loop (the shard groups are collective)
+        # the four parts (sampling.py), each resolved here: host coefficients, plans and buffers.  Everything that can
+        # fail has failed before the first kernel
+        plan = overlap_plan(windows, F) if raw_weights is None else weighted_overlap_plan(windows, F, raw_weights)
+        stitch = Stitch(plan, raw_weights is not None, blend_kind, nW, C, F, hw, len(timesteps), dev)
+        self.last_overlap = stitch.report
+        guidance = Guidance(row_names, guidance_scale, audio_guidance_scale, guidance_rescale, guided, kps_tokens, audio,
+                            lambda audio_is_zero, half_rows: self._unit_plan(latents, kps_tokens, audio, audio_is_zero,
+                                                                             windows, win_ids, half_rows),
+                            nW, C, f, hw, dev)
+        self.last_schedule, self.last_guidance = guidance.schedule, guidance.report
         preds = torch.empty((nW, C, f, hw), device=dev, dtype=torch.float32)
-        # (the one-scale routes name their rows by index, as they always have; a silent row needs the triple)
-        half_rows = [GUIDANCE_ROWS[r] for r in row_names] if "m" in row_names else list(range(cond_rows))
-        plan_g = self._unit_plan(latents, kps_tokens, audio, audio_is_zero, windows, win_ids, half_rows)
-        self.last_schedule = plan_g["schedule"]
-        plan_c = None
-        if not all(guided):
-            plan_c = self._unit_plan(latents, kps_tokens, audio, audio_is_zero, windows, win_ids, [1])
-        self.last_guidance = dict(guided_steps=sum(guided) if do_cfg else 0, steps=len(timesteps),
-                                  rescale=guidance_rescale,
-                                  unguided_schedule=None if plan_c is None else plan_c["schedule"])
-        if audio_guidance_scale is not None:
-            self.last_guidance.update(rows=row_names, audio_scale=float(audio_guidance_scale))
-        rescale_ws = None
-        if guidance_rescale > 0.0 and any(guided):
-            rescale_ws = torch.empty(ops.guidance_rescale_ws_floats(nW, f, hw), device=dev, dtype=torch.float32)
-        # DPM-Solver++: the previous step's x0 of every frame (identical on every rank, like the latents) and the
-        # update coefficients of every step, resolved on the host before the loop
-        x0_hist = torch.empty_like(latents) if multistep else None
-        coefs = [self.scheduler.multistep_coefficients(begin_index + i, begin_index)
-                 for i in range(len(timesteps))] if multistep else None
-        if ancestral:
-            coefs = self._ancestral_coefficients(kind, timesteps, begin_index, eta)
-            noise_seed = int(noise_seed)
-        euler_a = kind == "euler-a"
-        # init-video sampling: the (a, s) of the start and of the blend after every step, resolved on the host
-        blend = None
-        if kmask is not None:
-            blend = [(1.0, 0.0) if i == len(timesteps) - 1 else self.scheduler.noise_coefficients(begin_index + i + 1)
-                     for i in range(len(timesteps))]
-        self.last_init = dict(begin_index=begin_index, masked=kmask is not None,
-                              blend_launches=0 if known is None else 1 + (len(timesteps) if blend else 0))
-        if known is not None:
-            # the start latents, in the frame the loop runs in (Euler ancestral: the VP frame, (init + sigma noise) /
-            # sqrt(1 + sigma^2))
-            ops.known_blend(latents, init, noise, None, *self.scheduler.noise_coefficients(begin_index))
-        elif euler_a and timesteps:
-            latents.mul_(1.0 / self.scheduler.frame_scale(begin_index))          # VE -> VP, once
+        sampler = Sampler(self.scheduler, kind, latents, timesteps, begin_index, eta, noise_seed)
+        known = Known(self.scheduler, init, noise, kmask, len(timesteps), begin_index)
+        self.last_init = known.report
+        if known.active:
+            known.start(latents)                      # (already in the frame the loop runs in)
+        else:
+            sampler.start(latents)
         for i, t in enumerate(timesteps):
             t = int(t)
-            step_plan = plan_g if guided[i] else plan_c
+            step_plan = guidance.plan(i)
             local, max_slots, uidx = step_plan["local"], step_plan["max_slots"], step_plan["uidx"]
-            for bank_rows, gathers, kps, ehs, akv, azero, f_loc, shard, s0, n_slots in step_plan["calls"]:
-                parts = [ops.gather_latents(latents, ids, reps=reps) for ids, reps in gathers]
+            for call in step_plan["calls"]:
+                parts = [ops.gather_latents(latents, ids, reps=reps) for ids, reps in call.gathers]
                 x_in = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
-                out = unet.forward_tokens(x_in, t, ehs, kps, b=len(bank_rows), f=f_loc, H=H, W=W,
-                                          batch_rows=bank_rows, audio_kv=akv, audio_zero=azero, frame_shard=shard)
+                out = unet.forward_tokens(x_in, t, call.ehs, call.kps, b=len(call.bank_rows), f=call.f_loc, H=H, W=W,
+                                          batch_rows=call.bank_rows, audio_kv=call.audio_kv,
+                                          audio_zero=call.audio_zero, frame_shard=call.shard)
                 # a call's units occupy consecutive send slots, in row order: one strided pack per call
-                ops.pack_rows(out, C, local[s0:s0 + n_slots])
+                ops.pack_rows(out, C, local[call.s0:call.s0 + call.n_slots])
             gathered = dc.all_gather_units(local, max_slots)          # [world, max_slots, (f/G)*hw, C]
-            if three and guided[i]:
-                # u + s (m - u) + s_a (c - m) of every window, rescaled towards the conditional row's spread or not
-                if rescale_ws is not None:
-                    ops.guidance_rescale3(gathered, uidx, C, f, hw, guidance_scale, audio_guidance_scale,
-                                          guidance_rescale, rescale_ws, preds)
-                else:
-                    ops.combine_units3(gathered, uidx, C, f, hw, guidance_scale, audio_guidance_scale, preds)
-            elif rescale_ws is not None and guided[i]:
-                # the CFG combine with each window's prediction rescaled towards the conditional one's spread
-                ops.guidance_rescale(gathered, uidx, C, f, hw, scale2, guidance_rescale, rescale_ws, preds)
-            else:
-                # CFG combine of every window in one launch (:548-550; without CFG, and in an unguided step, the
-                # conditional prediction itself)
-                ops.combine_units(gathered, uidx, C, f, hw, scale2 if do_cfg and guided[i] else 1.0, preds)
-            step_preds = preds
-            if blended is not None:
-                ops.overlap_blend(preds, blend_terms, blend_w, blended)
-                step_preds = blended
-            if multistep:
-                ops.overlap_multistep_step(latents, step_preds, terms, frame_ids, counts, x0_hist, coefs[i])
-            elif ancestral:
-                ops.overlap_ancestral_step(latents, step_preds, terms, frame_ids, counts, coefs[i], noise_seed,
-                                           begin_index + i)
-            else:
-                ops.overlap_ddim_step(latents, step_preds, terms, frame_ids, counts,
-                                      self.scheduler.step_coefficients(t))
-            if blend is not None:
-                # the kept part again, at the level the latents have now (init itself after the last step)
-                ops.known_blend(latents, init, noise, kmask, *blend[i])
+            guidance.combine(i, gathered, uidx, preds)
+            sampler.update(i, t, latents, stitch.reduce(preds), stitch)
+            known.after(i, latents)
             if callback is not None and i % callback_steps == 0:
-                # Euler ancestral: the callback sees the scheduler's own (VE) frame, as the reference's does
-                callback(i, t, latents * self.scheduler.frame_scale(begin_index + i + 1) if euler_a else latents)
-        if euler_a and timesteps:
-            scale = self.scheduler.frame_scale(begin_index + len(timesteps))
-            if scale != 1.0:                                                     # a run that stops before sigma = 0
-                latents.mul_(scale)
+                callback(i, t, sampler.callback_view(i, latents))
+        sampler.finish(latents)
         return latents
 
     @torch.no_grad()
@@ -685,14 +575,19 @@ class VExpressPipeline:
         # an unsupported scheduler, eta with one other than DDIM, guidance controls out of range or init-video arguments
         # that do not fit the clip fail here, before the prologue
         kind = self._sampler(eta)
+        ancestral = kind in ANCESTRAL
         check_guidance(guidance_rescale, guidance_start, guidance_end, max(int(num_inference_steps), 1))
         audio_guidance_scale = check_audio_guidance(audio_guidance_scale)
-        windows = None
-        if check_blend(overlap_blend, int(context_frames)) != "mean":
-            # a blend the schedule's windows cannot carry fails here too
-            windows = list(get_context_scheduler(context_schedule)(
+
+        def clip_windows():
+            return list(get_context_scheduler(context_schedule)(
                 step=0, num_frames=video_length, context_size=context_frames, context_stride=1,
                 context_overlap=context_overlap, closed_loop=False))
+        windows = None
+        if check_blend(overlap_blend, int(context_frames)) != "mean":
+            # a blend the schedule's windows cannot carry fails here too; the mean's windows come after the prologue, as
+            # they always have (an unknown schedule fails there)
+            windows = clip_windows()
             if not isinstance(overlap_blend, str):
                 overlap_blend = [float(v) for v in overlap_blend][:len(windows[0])]   # (one short window: F < f)
             blend_weights(windows, overlap_blend)
@@ -710,8 +605,8 @@ class VExpressPipeline:
         init_t = min(int(num_inference_steps * strength), num_inference_steps)
         begin_index = max(num_inference_steps - init_t, 0)
         timesteps = self.scheduler.timesteps[begin_index:].tolist()
-        if kind in ("ddim-eta", "euler-a"):
-            self._ancestral_coefficients(kind, timesteps, begin_index, eta)     # e.g. eta too large: ValueError here
+        if ancestral:
+            ancestral_coefficients(self.scheduler, kind, timesteps, begin_index, eta)   # e.g. eta too large: ValueError here
         writer = ReferenceAttentionControl(self.reference_net, do_classifier_free_guidance=do_cfg, mode="write",
                                            batch_size=1, fusion_blocks="full")
         reader = ReferenceAttentionControl(self.denoising_unet, do_classifier_free_guidance=do_cfg, mode="read",
@@ -730,9 +625,7 @@ class VExpressPipeline:
             audio_embeddings = self.prepare_audio_embeddings(audio_waveform, video_length, num_pad_audio_frames,
                                                              do_cfg)
         if windows is None:
-            windows = list(get_context_scheduler(context_schedule)(
-                step=0, num_frames=video_length, context_size=context_frames, context_stride=1,
-                context_overlap=context_overlap, closed_loop=False))
+            windows = clip_windows()
         # ReferenceNet once per clip (:502-509)
         ehs0 = torch.zeros((1, 1, self.denoising_unet.cfg.cross_attention_dim), dtype=torch.float32, device=dev)
         self.reference_net(reference_latents.to(dev), timestep=0, encoder_hidden_states=ehs0, return_dict=False)
@@ -762,7 +655,7 @@ class VExpressPipeline:
             m = None if pixel_mask is None else latent_mask(pixel_mask, video_length, self.vae_scale_factor).to(dev)
             known = (init, noise, m)
             lat = torch.empty_like(noise)
-        if kind in ("ddim-eta", "euler-a") and noise_seed is None:
+        if ancestral and noise_seed is None:
             # the ancestral noise is drawn on the device from one 64-bit seed, taken from the generator AFTER the
             # initial latents (which so stay what they are for a given generator); rank 0's seed wins, like its latents
             g = generator[0] if isinstance(generator, list) else generator

@@ -1,0 +1,244 @@
+"""The four parts of `VExpressPipeline.denoise`, each resolved once before the loop into an object that holds its own
+buffers and host-side coefficients, so that a timestep reads straight down:
+    UNet calls of guidance.plan(i) -> all_gather_units -> guidance.combine -> stitch.reduce -> sampler.update -> known.after
+  Stitch    how the window predictions of a step become one prediction per frame: the mean plan, or the weighted pre-pass;
+  Guidance  which rows a step runs per window and the one launch that combines them (rescaled or not);
+  Sampler   the update of the scheduler in use, its per-step coefficients and, for Euler ancestral, the VE <-> VP frame;
+  Known     the known region of init-video sampling: the start latents and the blend after every step.
+A choice that does not depend on the timestep is made in a constructor (a method bound there), never in the loop.  Every
+kernel wrapper is looked up as `ops.<name>` when it is called: tests and tools replace them there."""
+from typing import Any, List, NamedTuple
+
+import torch
+
+from . import ops
+
+# the samplers that draw noise at every step (vx_overlap_ancestral_step)
+ANCESTRAL = ("ddim-eta", "euler-a")
+
+# The batch rows a window can run, as (bank row, keypoint row, audio row) of the CFG-layout conditioning (row 0 zeros,
+# row 1 real): "u" drops everything, "m" ("silent") keeps the reference bank and the keypoints and drops the audio, "c"
+# keeps everything.
+GUIDANCE_ROWS = {"u": (0, 0, 0), "m": (1, 1, 0), "c": (1, 1, 1)}
+
+
+class UnitCall(NamedTuple):
+    """One UNet call of a step plan (VExpressPipeline._unit_plan): the reference-bank row of every batch row; (frame ids
+    int32 [f_loc], repeats) of every window; the keypoint and audio tokens of the rows, the step-invariant audio K | V
+    (unet.precompute_audio_kv) and which rows carry all-zero audio; the frames of a window this rank computes and their
+    frame-shard group; the first send slot of the call and how many it fills."""
+    bank_rows: List[int]
+    gathers: list
+    kps: torch.Tensor
+    ehs: torch.Tensor
+    audio_kv: Any
+    audio_zero: List[bool]
+    f_loc: int
+    shard: Any
+    s0: int
+    n_slots: int
+
+
+def ancestral_coefficients(scheduler, kind, timesteps, begin_index, eta):
+    """Per-step (alpha_s, sigma_s, c_x, c_0, c_z) of an ancestral sampler, resolved on the host before the loop."""
+    if kind == "ddim-eta":
+        return [scheduler.ancestral_coefficients(t, eta) for t in timesteps]
+    return [scheduler.ancestral_coefficients(begin_index + i) for i in range(len(timesteps))]
+
+
+class Stitch:
+    """Mean of the overlapping predictions (the reference's 1 / count, summed inside the update) or, for a weighted blend,
+    one vx_overlap_blend launch per step into `blended`, one "window" of F frames that the update reads through the
+    trivial plan (one term, count 1).  Identical on every rank, like the update.  `report` is last_overlap."""
+
+    def __init__(self, plan, weighted, blend_kind, nW, C, F, hw, steps, dev):
+        # plan: context.overlap_plan, or context.weighted_overlap_plan for a weighted blend
+        if not weighted:
+            sf = plan["step_frames"]
+            terms = torch.full((len(sf), plan["max_terms"], 2), -1, dtype=torch.int32)
+            for i, fr in enumerate(sf):
+                for j, (wi, li) in enumerate(plan["terms"][fr]):
+                    terms[i, j, 0], terms[i, j, 1] = wi, li
+            self.terms = terms.to(dev)
+            self.frame_ids = torch.tensor(sf, dtype=torch.int32, device=dev)
+            self.counts = torch.tensor([float(plan["counts"][fr]) for fr in sf], dtype=torch.float32, device=dev)
+            self.blended, self._reduce = None, self._window_preds
+        else:
+            self.blend_terms = torch.from_numpy(plan["term_table"]).to(dev)
+            self.blend_w = torch.from_numpy(plan["weights"]).to(dev)
+            self.blended = torch.empty((1, C, F, hw), device=dev, dtype=torch.float32)
+            self.frame_ids = torch.arange(F, dtype=torch.int32, device=dev)
+            self.terms = torch.stack([torch.zeros_like(self.frame_ids), self.frame_ids], dim=1).view(F, 1, 2).contiguous()
+            self.counts = torch.ones(F, dtype=torch.float32, device=dev)
+            self._reduce = self._blend
+        self.report = dict(schedule=None, blend=blend_kind, windows=nW, max_terms=plan["max_terms"],
+                           blend_launches=0 if self.blended is None else steps)
+
+    def reduce(self, preds):
+        """The buffer the update reads: `preds` itself on the mean route, `blended` after one vx_overlap_blend."""
+        return self._reduce(preds)
+
+    def _window_preds(self, preds):
+        return preds
+
+    def _blend(self, preds):
+        ops.overlap_blend(preds, self.blend_terms, self.blend_w, self.blended)
+        return self.blended
+
+
+class Guidance:
+    """The rows of a guided step (`row_names`: guidance_rows), the plan of the guided steps and - only when some step runs
+    without guidance - the plan of the conditional row alone, and the one launch that turns a step's gathered units into
+    window predictions: vx_combine_units, vx_combine_units3, vx_guidance_rescale or vx_guidance_rescale3.
+    `unit_plan(half_rows)` builds a plan (VExpressPipeline._unit_plan, given the all-zero audio rows): collective, so both
+    plans are built here, on every rank, before the loop.  `report` is last_guidance, `schedule` last_schedule."""
+
+    def __init__(self, row_names, guidance_scale, audio_guidance_scale, rescale, guided, kps_tokens, audio, unit_plan,
+                 nW, C, f, hw, dev):
+        steps = len(guided)
+        do_cfg = len(row_names) > 1                   # a guided step combines rows
+        cond_rows = 2 if do_cfg else 1
+        if kps_tokens.shape[0] != cond_rows or audio.shape[0] != cond_rows:
+            what = f"guidance_scale={guidance_scale}"
+            if row_names in (("m", "c"), ("u", "m", "c")):
+                what += f" with audio_guidance_scale={audio_guidance_scale} (the silent row takes the zero-audio row 0)"
+            raise ValueError(f"{what} needs {cond_rows} batch row(s) of kps features / audio embeddings, got "
+                             f"{kps_tokens.shape[0]} / {audio.shape[0]}")
+        if not do_cfg:                                # nothing to rescale, nothing to switch off
+            rescale, guided = 0.0, [True] * steps
+        # which CFG halves carry all-zero audio tokens (the unconditional half, :403-405): one device reduction per clip
+        audio_is_zero = [bool((audio[hh] == 0).all().item()) for hh in range(audio.shape[0])]
+        # (the one-scale routes name their rows by index, as they always have; a silent row needs the triple)
+        half_rows = [GUIDANCE_ROWS[r] for r in row_names] if "m" in row_names else list(range(cond_rows))
+        self.plan_g = unit_plan(audio_is_zero, half_rows)
+        self.plan_c = None if all(guided) else unit_plan(audio_is_zero, [1])
+        self.schedule = self.plan_g["schedule"]
+        self.report = dict(guided_steps=sum(guided) if do_cfg else 0, steps=steps, rescale=rescale,
+                           unguided_schedule=None if self.plan_c is None else self.plan_c["schedule"])
+        if audio_guidance_scale is not None:
+            self.report.update(rows=row_names, audio_scale=float(audio_guidance_scale))
+        # the one scale of a two-row combine: (m, c) is guided by the audio scale; one row: u + 1 (u - u)
+        scale2 = (float(audio_guidance_scale) if row_names == ("m", "c") else guidance_scale) if do_cfg else 1.0
+        ws = None
+        if rescale > 0.0 and any(guided):
+            ws = torch.empty(ops.guidance_rescale_ws_floats(nW, f, hw), device=dev, dtype=torch.float32)
+        geo, s, s_a, self.workspace = (C, f, hw), guidance_scale, audio_guidance_scale, ws
+
+        # the launch of a guided step - u + s (m - u) + s_a (c - m) or the CFG combine (:548-550), each window rescaled
+        # towards its conditional row's spread or not - and of an unguided one: the conditional prediction itself
+        def rescale3(g, u, p): ops.guidance_rescale3(g, u, *geo, s, s_a, rescale, ws, p)
+        def combine3(g, u, p): ops.combine_units3(g, u, *geo, s, s_a, p)
+        def rescale2(g, u, p): ops.guidance_rescale(g, u, *geo, scale2, rescale, ws, p)
+        def combine2(g, u, p): ops.combine_units(g, u, *geo, scale2, p)
+        def conditional(g, u, p): ops.combine_units(g, u, *geo, 1.0, p)
+        if len(row_names) == 3:
+            guided_op = combine3 if ws is None else rescale3
+        else:
+            guided_op = combine2 if ws is None else rescale2
+        self.plans = [self.plan_g if g else self.plan_c for g in guided]
+        self.combines = [guided_op if g else conditional for g in guided]
+
+    def plan(self, i):
+        return self.plans[i]
+
+    def combine(self, i, gathered, uidx, preds):
+        self.combines[i](gathered, uidx, preds)
+
+
+class Sampler:
+    """The update of one frame set per timestep: "ddim" (vx_overlap_ddim_step), "dpm" (vx_overlap_multistep_step, with the
+    previous step's x0 of every frame in `x0_hist`: identical on every rank, like the latents) or an ancestral one
+    (vx_overlap_ancestral_step, noise keyed by `noise_seed` and the step index).  The coefficients of every step are
+    resolved on the host here.  Euler ancestral: the latents come and go in the scheduler's (VE) frame and the loop runs
+    in the VP frame x / sqrt(1 + sigma^2); `frame_scale` is the scheduler's, None for the others."""
+
+    def __init__(self, scheduler, kind, latents, timesteps, begin_index, eta, noise_seed):
+        self.begin_index, self.steps = begin_index, len(timesteps)
+        self.frame_scale = scheduler.frame_scale if kind == "euler-a" and timesteps else None
+        if kind == "dpm":
+            self.x0_hist = torch.empty_like(latents)
+            self.coefs = [scheduler.multistep_coefficients(begin_index + i, begin_index) for i in range(self.steps)]
+            self._update = self._multistep
+        elif kind in ANCESTRAL:
+            self.coefs = ancestral_coefficients(scheduler, kind, timesteps, begin_index, eta)
+            self.noise_seed = int(noise_seed)
+            self._update = self._ancestral
+        else:
+            self.coefs = [scheduler.step_coefficients(int(t)) for t in timesteps]
+            self._update = self._ddim
+
+    def start(self, latents):
+        if self.frame_scale is not None:
+            latents.mul_(1.0 / self.frame_scale(self.begin_index))               # VE -> VP, once
+
+    def update(self, i, t, latents, step_preds, stitch):
+        """The update of step i (timestep t) on the frames of the stitch's plan."""
+        self._update(i, latents, step_preds, stitch)
+
+    def _ddim(self, i, latents, step_preds, stitch):
+        ops.overlap_ddim_step(latents, step_preds, stitch.terms, stitch.frame_ids, stitch.counts, self.coefs[i])
+
+    def _multistep(self, i, latents, step_preds, stitch):
+        ops.overlap_multistep_step(latents, step_preds, stitch.terms, stitch.frame_ids, stitch.counts, self.x0_hist,
+                                   self.coefs[i])
+
+    def _ancestral(self, i, latents, step_preds, stitch):
+        ops.overlap_ancestral_step(latents, step_preds, stitch.terms, stitch.frame_ids, stitch.counts, self.coefs[i],
+                                   self.noise_seed, self.begin_index + i)
+
+    def callback_view(self, i, latents):
+        """What a callback sees after step i: the scheduler's own (VE) frame for Euler ancestral, as the reference's."""
+        if self.frame_scale is None:
+            return latents
+        return latents * self.frame_scale(self.begin_index + i + 1)
+
+    def finish(self, latents):
+        if self.frame_scale is not None:
+            scale = self.frame_scale(self.begin_index + self.steps)
+            if scale != 1.0:                                                     # a run that stops before sigma = 0
+                latents.mul_(scale)
+
+
+def check_known(known, latents):
+    """Validates the `known` argument of denoise against the latents; returns (init, noise, mask), all None without it."""
+    if known is None:
+        return None, None, None
+    init, noise, kmask = known
+    for t, name in ((init, "init"), (noise, "noise")):
+        if tuple(t.shape) != tuple(latents.shape):
+            raise ValueError(f"known: {name} must be shaped like the latents {tuple(latents.shape)}, got "
+                             f"{tuple(t.shape)}")
+    want = (latents.shape[2], latents.shape[3] * latents.shape[4])
+    if kmask is not None and tuple(kmask.shape) != want:
+        raise ValueError(f"known: the latent mask must be [F, h * w] = {list(want)}, got {tuple(kmask.shape)}")
+    return init, noise, kmask
+
+
+class Known:
+    """Init-video sampling: (init, noise, mask) of check_known and the scheduler's (a, s) of the start and of the blend
+    after every step, resolved on the host.  `start` forms the start latents a_b init + s_b noise in the frame the loop
+    runs in (Euler ancestral: the VP frame, (init + sigma noise) / sqrt(1 + sigma^2)); `after` puts the kept part back at
+    the level the latents have after step i (init itself after the last step) - with a mask only.  `report` is last_init."""
+
+    def __init__(self, scheduler, init, noise, mask, steps, begin_index):
+        self.init, self.noise, self.mask, self._after = init, noise, mask, self._nothing
+        self.active = init is not None
+        self.scheduler, self.begin_index = scheduler, begin_index
+        if mask is not None:
+            self.blend = [(1.0, 0.0) if i == steps - 1 else scheduler.noise_coefficients(begin_index + i + 1)
+                          for i in range(steps)]
+            self._after = self._blend
+        self.report = dict(begin_index=begin_index, masked=mask is not None,
+                           blend_launches=(1 + (steps if mask is not None else 0)) if self.active else 0)
+
+    def start(self, latents):
+        ops.known_blend(latents, self.init, self.noise, None, *self.scheduler.noise_coefficients(self.begin_index))
+
+    def after(self, i, latents):
+        self._after(i, latents)
+
+    def _nothing(self, i, latents):
+        """No mask (plain img2img, or no init clip at all): nothing after the start."""
+
+    def _blend(self, i, latents):
+        ops.known_blend(latents, self.init, self.noise, self.mask, *self.blend[i])
