@@ -354,6 +354,10 @@ int vx_layernorm_fp8(const void* x, int ldx, int rows, int c, float eps, const f
  * (modules/mutual_self_attention.py:177-224) and the sd-vae-ft-mse mid-block attention.
  * q: bf16 rows [batch*n_q] with row stride ldq, head h at column h*head_dim; k likewise (kv batch = batch / q_per_kv);
  * vt: bf16 [kv_batches, heads, head_dim, vt_pitch] (keys contiguous); out: bf16 rows, stride ldo.
+ * The caller keeps the pitch padding - columns [n_kv, vt_pitch) of every V^T row - ZERO: the kernels load V^T eight keys at
+ * a time up to the pitch and multiply the padding by a probability of exactly 0, so a NaN / Inf there would reach the
+ * output (v_express_amd.ops.alloc_vt zero-fills it; the VX_PART_VT epilogue of vx_gemm writes keys [0, seq_len) only and
+ * never touches it).  Nothing beyond the pitch, beyond row n_q / n_kv of q / k or beyond column heads * head_dim is read.
  * scale = 0: K already carries scale * log2(e) (the model folds it into the to_k weights at load time, so neither
  * operand is rounded twice): softmax_j 2^(q . k_j), no multiply in the kernel. */
 int vx_attention(const void* q, int ldq, const void* k, int ldk, const void* vt, int vt_pitch, void* out, int ldo,
