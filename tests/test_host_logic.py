@@ -35,52 +35,6 @@ def test_c_abi_library_loads_and_exports_every_declared_symbol():
         lib.check(rc, "vx_gemm")
 
 
-def test_gemm_params_struct_matches_header_layout():
-    """Compile a 3-line C probe against include/vexpress_hip.h and compare sizeof/offsets with the ctypes mirror."""
-    import subprocess
-    import tempfile
-    from v_express_amd import lib
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "vexpress_hip.h"
-int main(void){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(vx_gemm_params), offsetof(vx_gemm_params, w),
-  offsetof(vx_gemm_params, alpha), offsetof(vx_gemm_params, residual), offsetof(vx_gemm_params, part_out),
-  offsetof(vx_gemm_params, vt_pitch), offsetof(vx_gemm_params, ring_hint), offsetof(vx_gemm_params, ln_eps),
-  offsetof(vx_gemm_params, coop_epoch)); return 0; }'''
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "p.c"), "w").write(src)
-        inc = os.path.join(os.path.dirname(lib.HEADER))
-        subprocess.check_call(["gcc", "-I", inc, os.path.join(d, "p.c"), "-o", os.path.join(d, "p")])
-        got = list(map(int, subprocess.check_output([os.path.join(d, "p")]).split()))
-    G = lib.GemmParams
-    assert got == [ctypes.sizeof(G), G.w.offset, G.alpha.offset, G.residual.offset, G.part_out.offset,
-                   G.vt_pitch.offset, G.ring_hint.offset, G.ln_eps.offset, G.coop_epoch.offset]
-
-
-def test_axattn_params_struct_matches_header_layout():
-    """vx_axattn_params (ABI 15): the ctypes mirror against a C probe compiled from include/vexpress_hip.h; and the entry
-    point validates its arguments before any launch (no GPU needed)."""
-    import subprocess
-    import tempfile
-    from v_express_amd import lib
-    fields = ["ldx", "out", "rows", "rows_per_frame", "ln_stats", "ln_eps", "kq", "vo", "bias_o", "alpha", "row_stats_out",
-              "row_stats_parts", "row_stats_eps"]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "vexpress_hip.h"\nint main(void){ printf("%zu", sizeof(vx_axattn_params));\n' +
-           "".join(f'printf(" %zu", offsetof(vx_axattn_params, {f}));\n' for f in fields) + 'printf("\\n"); return 0; }\n')
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "p.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.dirname(lib.HEADER), os.path.join(d, "p.c"), "-o", os.path.join(d, "p")])
-        got = list(map(int, subprocess.check_output([os.path.join(d, "p")]).split()))
-    A = lib.AxAttnParams
-    assert got == [ctypes.sizeof(A)] + [getattr(A, f).offset for f in fields]
-    assert lib.lib.vx_audio_xattn_supported(320, 8, 5, 4096) == 1 and lib.lib.vx_audio_xattn_supported(1280, 8, 5, 64) == 1
-    assert lib.lib.vx_audio_xattn_supported(320, 8, 4, 4096) == 0 and lib.lib.vx_audio_xattn_supported(64, 8, 5, 64) == 0
-    assert lib.lib.vx_audio_xattn_packed_bytes(320, 16) == 16 * 320 * 96
-    rc = lib.lib.vx_audio_xattn(ctypes.byref(A()), None)
-    assert rc < 0 and b"vx_audio_xattn" in lib.lib.vx_last_error_string()
-
-
 def test_windows_and_alignment_match_reference_context_py():
     gold = torch.load(os.path.join(os.path.dirname(__file__), "golden", "windows.pt"), weights_only=False)
     for (F, cs, co), ref in gold.items():

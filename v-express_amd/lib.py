@@ -6,88 +6,26 @@ raises.  The library is built in-tree (v-express_amd/libvexpress_hip.so) by `__g
 """
 import ctypes as C
 import os
-import re
 import subprocess
+
+from . import abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VX_LIBRARY: another build of the SAME library (same-box A/B runs of kernel variants, tools/ only); default in-tree
 LIB_PATH = os.environ.get("VX_LIBRARY") or os.path.join(_HERE, "libvexpress_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-HEADER = os.path.join(os.path.dirname(_HERE), "include", "vexpress_hip.h")
+HEADER = abi.HEADER
 
-VX_EPI_STORE, VX_EPI_GEGLU, VX_EPI_SPLIT = 0, 1, 2
-VX_PART_ROWS, VX_PART_VT = 0, 1
-VX_ACT_NONE, VX_ACT_SILU, VX_ACT_GELU = 0, 1, 2
-
-
-class FfParams(C.Structure):
-    """Mirror of `vx_ff_params` (include/vexpress_hip.h)."""
-    _fields_ = [
-        ("x", C.c_void_p), ("ldx", C.c_int32), ("m", C.c_int32), ("c", C.c_int32), ("hidden", C.c_int32),
-        ("w1t", C.c_void_p), ("w2t", C.c_void_p), ("bias1", C.c_void_p), ("ln_colsum", C.c_void_p),
-        ("ln_stats", C.c_void_p), ("bias2", C.c_void_p), ("residual", C.c_void_p), ("ldr", C.c_int32),
-        ("out", C.c_void_p), ("ldo", C.c_int32),
-    ]
-
-
-class AxAttnParams(C.Structure):
-    """Mirror of `vx_axattn_params` (include/vexpress_hip.h)."""
-    _fields_ = [
-        ("x", C.c_void_p), ("ldx", C.c_int32), ("out", C.c_void_p), ("ldo", C.c_int32), ("rows", C.c_int32), ("c", C.c_int32),
-        ("rows_per_frame", C.c_int32), ("ln_stats", C.c_void_p), ("ln_stats_parts", C.c_int32), ("ln_eps", C.c_float),
-        ("kq", C.c_void_p), ("kq_colsum", C.c_void_p), ("kq_bias", C.c_void_p), ("vo", C.c_void_p), ("bias_o", C.c_void_p),
-        ("alpha", C.c_float), ("row_stats_out", C.c_void_p), ("row_stats_parts", C.c_int32), ("row_stats_eps", C.c_float),
-    ]
-
-
-class TBlockParams(C.Structure):
-    """Mirror of `vx_tblock_params` (include/vexpress_hip.h)."""
-    _fields_ = [
-        ("x", C.c_void_p), ("ldx", C.c_int32), ("b", C.c_int32), ("f", C.c_int32), ("hw", C.c_int32), ("c", C.c_int32),
-        ("heads", C.c_int32), ("wqkv_t", C.c_void_p), ("wo_t", C.c_void_p), ("colsum_p", C.c_void_p), ("bias_o", C.c_void_p), ("ln_stats", C.c_void_p), ("stats_out", C.c_void_p), ("ln_eps", C.c_float),
-        ("scale", C.c_float),
-    ]
-
-
-class GemmParams(C.Structure):
-    """Mirror of `vx_gemm_params` (include/vexpress_hip.h).""" 
-    _fields_ = [
-        ("a", C.c_void_p), ("a2", C.c_void_p),
-        ("c1", C.c_int32), ("c2", C.c_int32),
-        ("lda1", C.c_int32), ("lda2", C.c_int32),
-        ("nb", C.c_int32), ("h_in", C.c_int32), ("w_in", C.c_int32),
-        ("kh", C.c_int32), ("kw", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
-        ("upsample", C.c_int32),
-        ("h_out", C.c_int32), ("w_out", C.c_int32),
-        ("w", C.c_void_p),
-        ("n", C.c_int32), ("k", C.c_int32), ("m", C.c_int32),
-        ("epi", C.c_int32), ("act", C.c_int32),
-        ("alpha", C.c_float),
-        ("bias", C.c_void_p), ("rowbias", C.c_void_p),
-        ("rowbias_ld", C.c_int32), ("rows_per_group", C.c_int32),
-        ("residual", C.c_void_p), ("ldr", C.c_int32),
-        ("out", C.c_void_p), ("ldc", C.c_int32), ("out_f32", C.c_int32),
-        ("part_cols", C.c_int32), ("n_parts", C.c_int32),
-        ("part_out", C.c_void_p * 3), ("part_kind", C.c_int32 * 3), ("part_ld", C.c_int32 * 3),
-        ("seq_len", C.c_int32), ("head_dim", C.c_int32), ("vt_pitch", C.c_int32),
-        ("splitk", C.c_int32), ("splitk_ws", C.c_void_p),
-        ("ring_hint", C.c_int32),
-        ("a_fp8", C.c_int32), ("a_scale", C.c_void_p), ("w_scale", C.c_void_p),
-        ("ln_stats", C.c_void_p), ("ln_colsum", C.c_void_p),
-        ("row_stats_out", C.c_void_p), ("row_stats_eps", C.c_float),
-        ("w_group_rows", C.c_int32),
-        ("gn_ws", C.c_void_p), ("gn_groups", C.c_int32), ("gn_hw", C.c_int32),
-        ("row_stats_parts", C.c_int32), ("ln_stats_parts", C.c_int32), ("ln_eps", C.c_float),
-        ("coop_epoch", C.c_int32),
-    ]
+# the binding is DERIVED from the header (abi.py reads it once per process): the enum constants, the ctypes mirrors of the
+# four parameter structs and, in _load, argtypes / restype of every function - there is no second copy to keep in step
+globals().update(abi.header().enums)                 # VX_EPI_*, VX_PART_*, VX_ACT_*
+GemmParams, FfParams, TBlockParams, AxAttnParams = (
+    abi.header().classes[s] for s in ("vx_gemm_params", "vx_ff_params", "vx_tblock_params", "vx_axattn_params"))
 
 
 def declared_symbols():
     """Every function name declared in include/vexpress_hip.h."""
-    with open(HEADER) as f:
-        text = f.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(vx_[a-z0-9_]+)\s*\(", text)))
+    return sorted(abi.header().functions)
 
 
 def build(force=False):
@@ -109,82 +47,10 @@ def _load(path=None, element="bf16"):
     missing = [s for s in declared_symbols() if not hasattr(lib, s)]
     if missing:
         raise ImportError(f"{path} does not export {missing}; rebuild it")
-    i32, f32, vp, i64 = C.c_int32, C.c_float, C.c_void_p, C.c_int64
-    lib.vx_last_error_string.restype = C.c_char_p
-    lib.vx_abi_version.restype = i32
-    lib.vx_device_info.argtypes = [i32, C.POINTER(i32)]
-    lib.vx_gemm.argtypes = [C.POINTER(GemmParams), vp]
-    lib.vx_gemm_config_name.argtypes = [C.POINTER(GemmParams)]
-    lib.vx_gemm_config_name.restype = C.c_char_p
-    lib.vx_gemm_last_kernel.restype = C.c_char_p
-    lib.vx_last_kernel.restype = C.c_char_p
-    lib.vx_build_id.restype = C.c_char_p
-    lib.vx_element_type.restype = C.c_char_p
-    lib.vx_gemm_splitk_ws_bytes.argtypes = [i32, i32, i32]
-    lib.vx_gemm_splitk_ws_bytes.restype = i64
-    lib.vx_gemm_ring_coop_ok.argtypes = [C.POINTER(GemmParams)]
-    lib.vx_groupnorm_ws_floats.restype = i64
-    lib.vx_groupnorm_ws_floats.argtypes = [i32, i32, i32]
-    lib.vx_groupnorm.argtypes = [vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, vp, i32, i32, i32, vp]
-    lib.vx_groupnorm_stats.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, i32, vp]
-    lib.vx_groupnorm_apply.argtypes = [vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp]
-    lib.vx_gemm_gn_slabs.argtypes = [C.POINTER(GemmParams)]
-    lib.vx_ff_fused.argtypes = [C.POINTER(FfParams), vp]
-    lib.vx_ff_pack_weights.argtypes = [vp, vp, vp, vp, i32, i32, vp]
-    lib.vx_tblock_fused.argtypes = [C.POINTER(TBlockParams), vp]
-    lib.vx_tblock_pack.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp]
-    lib.vx_tblock_packed_bytes.argtypes = [i32]
-    lib.vx_tblock_packed_bytes.restype = i64
-    lib.vx_audio_xattn_packed_bytes.argtypes = [i32, i32]
-    lib.vx_audio_xattn_packed_bytes.restype = i64
-    lib.vx_audio_xattn_supported.argtypes = [i32, i32, i32, i32]
-    lib.vx_audio_xattn_pack.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.vx_audio_xattn.argtypes = [C.POINTER(AxAttnParams), vp]
-    lib.vx_groupnorm_fold_linear.argtypes = [vp, i32, i32, i32, i32, f32, vp, i32, vp, vp, i32, vp, vp, vp]
-    lib.vx_layernorm.argtypes = [vp, i32, i32, i32, f32, vp, vp, vp, i32, i32, vp, i32, vp]
-    lib.vx_row_stats.argtypes = [vp, i32, i32, i32, f32, vp, vp]
-    lib.vx_row_stats_parts.argtypes = [vp, i32, i32, i32, vp, vp]
-    lib.vx_row_stats_finalize.argtypes = [vp, i32, i32, f32, vp, vp]
-    lib.vx_layernorm_fp8.argtypes = [vp, i32, i32, i32, f32, vp, vp, vp, i32, i32, vp, i32, vp, vp]
-    lib.vx_attention.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
-    lib.vx_attention_bounded.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp]
-    lib.vx_key_norm_max.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
-    lib.vx_temporal_attention.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp]
-    lib.vx_small_kv_attention.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp]
-    lib.vx_add_row_bias.argtypes = [vp, i32, i32, i32, vp, f32, vp]
-    lib.vx_add_residual_f32.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, vp]
-    lib.vx_pad_image.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    lib.vx_pixel_shuffle2x.argtypes = [vp, i64, i32, i32, i32, i32, vp, vp]
-    lib.vx_gather_latents.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp]
-    lib.vx_cfg_combine.argtypes = [vp, i32, i32, i32, i32, f32, vp, vp]
-    lib.vx_pack_rows.argtypes = [vp, i32, i64, i32, vp, vp]
-    lib.vx_combine_units.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp]
-    lib.vx_guidance_rescale_ws_floats.restype = i64
-    lib.vx_guidance_rescale_ws_floats.argtypes = [i32, i32, i32]
-    lib.vx_guidance_rescale.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, i64, vp, vp]
-    lib.vx_combine_units3.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp]
-    lib.vx_guidance_rescale3.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, i64, vp, vp]
-    lib.vx_overlap_ddim_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, f32, f32, f32, f32, vp]
-    lib.vx_overlap_multistep_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, f32, f32, f32, f32,
-                                              f32, vp]
-    lib.vx_overlap_ancestral_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, f32, f32, f32, f32,
-                                              f32, C.c_uint32, C.c_uint32, i32, vp]
-    lib.vx_overlap_blend.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp]
-    lib.vx_known_blend.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, vp]
-    lib.vx_vae_postprocess_composite.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp]
-    lib.vx_ncfhw_to_nhwc.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
-    lib.vx_nhwc_to_ncfhw.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
-    lib.vx_vae_postprocess.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    lib.vx_median3d.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.vx_wave_conv1d.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp]
-    for name in declared_symbols():
+    for name, (restype, params) in abi.header().functions.items():
         fn = getattr(lib, name)
-        if name not in ("vx_last_error_string", "vx_groupnorm_ws_floats", "vx_guidance_rescale_ws_floats",
-                        "vx_gemm_config_name",
-                        "vx_gemm_splitk_ws_bytes", "vx_gemm_last_kernel", "vx_last_kernel", "vx_build_id",
-                        "vx_tblock_packed_bytes", "vx_element_type", "vx_audio_xattn_packed_bytes"):
-            fn.restype = i32
-    if lib.vx_abi_version() != 15:
+        fn.restype, fn.argtypes = restype, [ctype for _, ctype in params]
+    if lib.vx_abi_version() != abi.header().version:
         raise ImportError(f"{os.path.basename(path)} ABI version mismatch")
     if lib.vx_element_type().decode() != element:
         raise ImportError(f"{path} computes on {lib.vx_element_type().decode()} elements, expected {element}")
