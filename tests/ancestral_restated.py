@@ -1,9 +1,8 @@
 """float64 restatements of ancestral sampling (TEST INFRASTRUCTURE) for tests/test_ancestral_cpu.py and
 tests/test_gpu_ancestral_sampling.py: the counter-based noise of v-express_amd/csrc/vx_rng.h (Philox4x32-10 of
 Random123 + Box-Muller, keyed by (seed, step, frame, channel, pixel)), the textbook updates of diffusers==0.29.2
-`DDIMScheduler.step` with eta and `EulerAncestralDiscreteScheduler.step` (v-prediction), the mean-overlap loop of
-pipelines/v_express_pipeline.py:526-583 with one update per frame per timestep and this noise, and an emulated
-`ops.overlap_ancestral_step` in the style of tests/fake_ops.py."""
+`DDIMScheduler.step` with eta and `EulerAncestralDiscreteScheduler.step` (v-prediction), and an emulated
+`ops.overlap_ancestral_step` in the style of tests/fake_ops.py.  The loop that uses them is tests/loop_restated.py."""
 import math
 
 import numpy as np
@@ -85,51 +84,6 @@ def ddim_table(n, abar=None):
         p = t - 1000 // n
         out.append((float(abar[t]), float(abar[p]) if p >= 0 else 1.0))
     return out
-
-
-# ------------------------------------------------------------------------------------------------ restated loop
-def restated_loop(unet_fn, latents, windows, guidance_scale, kps_feature, audio_embeddings, n, sampler, seed, eta=1.0):
-    """pipelines/v_express_pipeline.py:526-583 with an ancestral update of each frame once per timestep, in float64, the
-    noise of each frame the counter-based one above.  sampler "ddim-eta" (float64 zero-SNR table) or "euler-a" (VE frame,
-    starting from latents x init_noise_sigma, the UNet fed x_ve / sqrt(1 + sigma^2)).  Returns the final latents."""
-    do_cfg = guidance_scale > 1.0
-    lat = latents.double().clone()
-    _, c, F_, h, w = lat.shape
-    if sampler == "euler-a":
-        sg = D.sigmas(n)
-        lat = lat * sg[0]
-    else:
-        tab = ddim_table(n)
-    count = torch.zeros(F_, dtype=torch.long)
-    for ctx in windows:
-        count[ctx] += 1
-    for i, t in enumerate(D.timesteps(n)):
-        scale = 1.0 / math.sqrt(1.0 + sg[i] ** 2) if sampler == "euler-a" else 1.0
-        counter = torch.zeros(F_, dtype=torch.long)
-        pending, final = [None] * F_, {}
-        for ctx in windows:
-            aud = audio_embeddings[:, ctx]
-            inp = (lat[:, :, ctx] * scale).float().repeat(2 if do_cfg else 1, 1, 1, 1, 1)
-            pred = unet_fn(inp, t, aud.reshape(-1, aud.shape[-2], aud.shape[-1]), kps_feature[:, :, ctx]).double()
-            if do_cfg:
-                u, cd = pred.chunk(2)
-                pred = u + guidance_scale * (cd - u)
-            counter[ctx] += 1
-            pred = pred / count[ctx][None, None, :, None, None].double()
-            for li, fi in enumerate(ctx):
-                pending[fi] = pred[:, :, li].clone() if pending[fi] is None else pending[fi] + pred[:, :, li]
-                if counter[fi] == count[fi]:
-                    final[fi] = pending[fi]
-                    pending[fi] = None
-        x = lat.clone()
-        for fi, v in final.items():
-            z = noise_like(seed, i, fi, c, h, w)[None]
-            if sampler == "euler-a":
-                lat[:, :, fi] = euler_a_update_ve(sg[i], sg[i + 1], x[:, :, fi], v, z)
-            else:
-                a, ap = tab[i]
-                lat[:, :, fi] = ddim_eta_update(a, ap, eta, x[:, :, fi], v, z)
-    return lat
 
 
 def overlap_ancestral_step(latents, preds, terms, frame_ids, counts, coef, seed, step_index):

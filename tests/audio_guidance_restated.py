@@ -1,15 +1,13 @@
 """float64 restatements of three-row guidance (TEST INFRASTRUCTURE) for tests/test_audio_guidance_cpu.py and
 tests/test_gpu_audio_guidance.py: the guided prediction g = u + s (m - u) + s_a (c - m) of a separate audio scale (u: no
 condition; m, "silent": reference bank + keypoints, zero audio; c: everything), its rescale towards std(c) (diffusers'
-`rescale_noise_cfg` with the fully conditional row as the target), the mean-overlap loop of
-pipelines/v_express_pipeline.py:526-583 over the oracle UNet with any row set for every sampler, and emulated
-`ops.combine_units3` / `ops.guidance_rescale3` in the style of tests/fake_ops.py and guidance_restated.py."""
+`rescale_noise_cfg` with the fully conditional row as the target), the row rule, and emulated `ops.combine_units3` /
+`ops.guidance_rescale3` in the style of tests/fake_ops.py and guidance_restated.py.  The loop that uses them is
+tests/loop_restated.py."""
 import math
 
 import torch
 
-import ancestral_restated as A
-import dpm_restated as D
 import guidance_restated as G
 
 CHUNK = G.CHUNK
@@ -87,80 +85,3 @@ def guidance_rescale3(gathered, unit_index, c, f, hw, guidance, audio_guidance, 
             factor = 1.0 + phi * (math.sqrt(m2[0] / m2[1]) - 1.0)
         out[w] = (g[w].double() * factor).float()
     preds.copy_(out)
-
-
-def oracle_rows_unet(sd3, sd2, ocfg, ref_latents, w_ref, w_aud):
-    """The oracle UNet with a bank per batch row: fn(x [b, 4, f, h, w], t, audio [b * f, n_ctx, 768], kps [b, C0, f, h,
-    w], bank_rows) with bank_rows[i] = 1 for the reference bank and 0 for the all-zero one (what
-    ReferenceAttentionControl's cat([zeros, v]) gives rows 0 / 1; the oracle takes banks as plain [b, hw, C] tensors)."""
-    from oracle import unet as OU
-    ref = OU.refnet_banks(sd2, ocfg, ref_latents)
-
-    def fn(x, t, audio, kps, bank_rows):
-        banks = {k: torch.cat([v if r else torch.zeros_like(v) for r in bank_rows]) for k, v in ref.items()}
-        return OU.unet3d_forward(sd3, ocfg, x, t, audio, kps, banks, w_ref, w_aud)
-    return fn
-
-
-def restated_loop(unet_fn, latents, windows, s, s_a, kps_feature, audio_embeddings, n, sampler="ddim", phi=0.0,
-                  start=0.0, end=1.0, seed=None, eta=0.0, rows=None):
-    """guidance_restated.restated_loop with the rows of `rows_for(s, s_a)` per window (`unet_fn` of oracle_rows_unet;
-    kps_feature / audio_embeddings in the CFG layout, row 0 zeros): a guided step combines them in float64 as
-    u + s (m - u) + s_a (c - m) (three rows), m + s_a (c - m) (rows m, c) or u + s (c - u) (rows u, c) and rescales the
-    result towards std(c) for phi > 0; an unguided step takes the c row as it is."""
-    rows = rows_for(s, s_a) if rows is None else rows
-    assert len(rows) > 1
-    guided = G.guided_steps(n, start, end)
-    lat = latents.double().clone()
-    _, c, F_, h, w = lat.shape
-    sg = D.sigmas(n)
-    if sampler == "euler-a":
-        lat = lat * sg[0]
-    tab = A.ddim_table(n)
-    ords = D.orders(n)
-    hist = torch.zeros_like(lat)
-    count = torch.zeros(F_, dtype=torch.long)
-    for ctx in windows:
-        count[ctx] += 1
-    for i, t in enumerate(D.timesteps(n)):
-        scale = 1.0 / math.sqrt(1.0 + sg[i] ** 2) if sampler == "euler-a" else 1.0
-        counter = torch.zeros(F_, dtype=torch.long)
-        pending, final = [None] * F_, {}
-        names = rows if guided[i] else ("c",)
-        for ctx in windows:
-            trip = [ROWS[r] for r in names]
-            aud = torch.cat([audio_embeddings[a][ctx] for _, _, a in trip])
-            kps = torch.stack([kps_feature[k][:, ctx] for _, k, _ in trip])
-            inp = (lat[:, :, ctx] * scale).float().repeat(len(trip), 1, 1, 1, 1)
-            out = unet_fn(inp, t, aud, kps, [b for b, _, _ in trip]).double()
-            p = {r: out[j:j + 1] for j, r in enumerate(names)}
-            if not guided[i]:
-                pred = p["c"]
-            else:
-                if names == ("u", "m", "c"):
-                    pred = p["u"] + s * (p["m"] - p["u"]) + s_a * (p["c"] - p["m"])
-                elif names == ("m", "c"):
-                    pred = p["m"] + s_a * (p["c"] - p["m"])
-                else:
-                    pred = p["u"] + s * (p["c"] - p["u"])
-                if phi > 0.0:
-                    pred = G.rescale(pred, p["c"], phi)
-            counter[ctx] += 1
-            pred = pred / count[ctx][None, None, :, None, None].double()
-            for li, fi in enumerate(ctx):
-                pending[fi] = pred[:, :, li].clone() if pending[fi] is None else pending[fi] + pred[:, :, li]
-                if counter[fi] == count[fi]:
-                    final[fi] = pending[fi]
-                    pending[fi] = None
-        x = lat.clone()
-        for fi, v in final.items():
-            if sampler == "dpm":
-                lat[:, :, fi], hist[:, :, fi] = D.update(sg, i, ords[i], x[:, :, fi], v, hist[:, :, fi])
-            elif sampler == "euler-a":
-                z = A.noise_like(seed, i, fi, c, h, w)[None]
-                lat[:, :, fi] = A.euler_a_update_ve(sg[i], sg[i + 1], x[:, :, fi], v, z)
-            else:
-                z = A.noise_like(seed, i, fi, c, h, w)[None] if sampler == "ddim-eta" else 0.0
-                a, ap = tab[i]
-                lat[:, :, fi] = A.ddim_eta_update(a, ap, eta if sampler == "ddim-eta" else 0.0, x[:, :, fi], v, z)
-    return lat

@@ -31,21 +31,11 @@ def run(geometry, latent=8, device="cpu", frame_shards=1):
     return lat, dict(pipe.last_schedule), dict(pipe.last_guidance)
 
 
-def main(geometry, latent=8):
-    """CPU, under RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT: this rank's final latents and its two schedules."""
-    import torch.distributed as dist
-    import audio_guidance_restated as AG
-    from v_express_amd import ops
+def main(rank, geometry, latent=8):
+    """CPU, one rank of loop_worker.spawn_gloo: this rank's final latents and its two schedules."""
     torch.set_num_threads(2)
-    dist.init_process_group("gloo")
     W.emulate_kernels()
-    ops.guidance_rescale = G.guidance_rescale
-    ops.combine_units3 = AG.combine_units3
-    ops.guidance_rescale3 = AG.guidance_rescale3
-    out = run(geometry, latent)
-    dist.barrier()
-    dist.destroy_process_group()
-    return out
+    return run(geometry, latent)
 
 
 if __name__ == "__main__":

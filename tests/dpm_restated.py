@@ -1,8 +1,7 @@
 """float64 restatements of DPM-Solver++ multistep sampling (TEST INFRASTRUCTURE) for tests/test_dpm_solver_cpu.py and
 tests/test_gpu_dpm_solver.py: the schedule tables, diffusers' order rule and update (DPMSolverMultistepScheduler of
-diffusers==0.29.2, algorithm_type "dpmsolver++", solver_type "midpoint", v-prediction), the mean-overlap loop of
-pipelines/v_express_pipeline.py:526-583 with one update per frame per timestep, and an emulated
-`ops.overlap_multistep_step` in the style of tests/fake_ops.py."""
+diffusers==0.29.2, algorithm_type "dpmsolver++", solver_type "midpoint", v-prediction) and an emulated
+`ops.overlap_multistep_step` in the style of tests/fake_ops.py.  The loop that uses them is tests/loop_restated.py."""
 import math
 
 import numpy as np
@@ -85,48 +84,6 @@ def coefficients(sg, i, order):
         a_p, s_p = _alpha_sigma(sg[i - 1])
         B = 0.5 * A / ((lam[1] - (math.log(a_p) - math.log(s_p))) / h)
     return a_s, s_s, s_t / s_s, A + B, B
-
-
-def restated_loop(unet_fn, latents, windows, guidance_scale, kps_feature, audio_embeddings, n, sched_kw=None,
-                  callback=None):
-    """pipelines/v_express_pipeline.py:526-583 with a DPM-Solver++ update of each frame once per timestep, in float64.
-    The value a frame is stepped with is the one the reference's loop keeps (:552-572: a frame that completes twice in
-    one window, e.g. 9 of [8, 9, 10, 9], keeps the last); its history is that frame's previous x0.
-    unet_fn / kps_feature / audio_embeddings as in oracle.loop.mean_overlap.  Returns the final latents (float64)."""
-    kw = dict(solver_order=2, lower_order_final=True, euler_at_final=False, final="zero")
-    kw.update(sched_kw or {})
-    sg = sigmas(n, kw["final"])
-    ords = orders(n, kw["solver_order"], kw["lower_order_final"], kw["euler_at_final"], kw["final"])
-    do_cfg = guidance_scale > 1.0
-    lat = latents.double().clone()
-    F_ = lat.shape[2]
-    count = torch.zeros(F_, dtype=torch.long)
-    for ctx in windows:
-        count[ctx] += 1
-    hist = torch.zeros_like(lat)
-    for i, t in enumerate(timesteps(n)):
-        counter = torch.zeros(F_, dtype=torch.long)
-        pending, final = [None] * F_, {}
-        for ctx in windows:
-            aud = audio_embeddings[:, ctx]
-            inp = lat[:, :, ctx].float().repeat(2 if do_cfg else 1, 1, 1, 1, 1)
-            pred = unet_fn(inp, t, aud.reshape(-1, aud.shape[-2], aud.shape[-1]), kps_feature[:, :, ctx]).double()
-            if do_cfg:
-                u, c = pred.chunk(2)
-                pred = u + guidance_scale * (c - u)
-            counter[ctx] += 1
-            pred = pred / count[ctx][None, None, :, None, None].double()
-            for li, fi in enumerate(ctx):
-                pending[fi] = pred[:, :, li].clone() if pending[fi] is None else pending[fi] + pred[:, :, li]
-                if counter[fi] == count[fi]:
-                    final[fi] = pending[fi]
-                    pending[fi] = None
-        x = lat.clone()
-        for fi, v in final.items():
-            lat[:, :, fi], hist[:, :, fi] = update(sg, i, ords[i], x[:, :, fi], v, hist[:, :, fi])
-        if callback is not None:
-            callback(i, t, lat)
-    return lat
 
 
 def overlap_multistep_step(latents, preds, terms, frame_ids, counts, x0_history, coef):

@@ -1,5 +1,5 @@
 """One rank of tests/test_dpm_solver_cpu.py's two-rank gloo run (TEST INFRASTRUCTURE): the small-config denoising loop
-with a DPM-Solver++ scheduler under emulated kernels (tests/fake_ops.py + dpm_restated.overlap_multistep_step)."""
+with a DPM-Solver++ scheduler under emulated kernels (loop_worker.emulate_kernels)."""
 import os
 import sys
 
@@ -21,15 +21,8 @@ def run():
     return W.run_loop(pipe, F, CF, CO, STEPS, latent=LATENT, device="cpu")
 
 
-def main():
-    """Under RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT: this rank's final latents."""
-    import torch.distributed as dist
-    from v_express_amd import ops
+def main(rank):
+    """One rank of loop_worker.spawn_gloo: this rank's final latents."""
     torch.set_num_threads(2)
-    dist.init_process_group("gloo")
     W.emulate_kernels()
-    ops.overlap_multistep_step = D.overlap_multistep_step
-    lat = run()
-    dist.barrier()
-    dist.destroy_process_group()
-    return lat
+    return run()

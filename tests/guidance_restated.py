@@ -1,14 +1,13 @@
 """float64 restatements of the guidance controls (TEST INFRASTRUCTURE) for tests/test_guidance_cpu.py and
 tests/test_gpu_guidance.py: the CFG rescale of Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed"
 (diffusers' `rescale_noise_cfg`: g * (1 + phi (std(cond) / std(g) - 1)), unbiased std over everything but the batch
-axis), the guidance-interval step rule (diffusers' control_guidance_start / _end convention), the mean-overlap loop of
-pipelines/v_express_pipeline.py:526-583 with both for every sampler, and an emulated `ops.guidance_rescale` in the style
-of tests/fake_ops.py that forms and merges its partials in the kernel's order."""
+axis), the guidance-interval step rule (diffusers' control_guidance_start / _end convention), and an emulated
+`ops.guidance_rescale` in the style of tests/fake_ops.py that forms and merges its partials in the kernel's order.  The
+loop that uses them is tests/loop_restated.py."""
 import math
 
 import torch
 
-import ancestral_restated as A
 import dpm_restated as D
 
 KWARGS = D.KWARGS
@@ -79,58 +78,3 @@ def guidance_rescale(gathered, unit_index, c, f, hw, guidance, phi, workspace, p
             factor = 1.0 + phi * (math.sqrt(m2[0] / m2[1]) - 1.0)
         out[w] = (g[w].double() * factor).float()
     preds.copy_(out)
-
-
-def restated_loop(unet_fn, latents, windows, guidance_scale, kps_feature, audio_embeddings, n, sampler="ddim", phi=0.0,
-                  start=0.0, end=1.0, seed=None, eta=0.0):
-    """pipelines/v_express_pipeline.py:526-583 in float64 with one update per frame per timestep (sampler "ddim",
-    "ddim-eta", "dpm", "euler-a": the textbook updates of dpm_restated / ancestral_restated), the window's prediction
-    rescaled where the reference combines the halves (:548-550) and, in an unguided step, the conditional prediction
-    taken as it is.  The oracle UNet's rows are independent, so an unguided step reads the conditional row of the pair."""
-    assert guidance_scale > 1.0
-    guided = guided_steps(n, start, end)
-    lat = latents.double().clone()
-    _, c, F_, h, w = lat.shape
-    sg = D.sigmas(n)
-    if sampler == "euler-a":
-        lat = lat * sg[0]
-    tab = A.ddim_table(n)
-    ords = D.orders(n)
-    hist = torch.zeros_like(lat)
-    count = torch.zeros(F_, dtype=torch.long)
-    for ctx in windows:
-        count[ctx] += 1
-    for i, t in enumerate(D.timesteps(n)):
-        scale = 1.0 / math.sqrt(1.0 + sg[i] ** 2) if sampler == "euler-a" else 1.0
-        counter = torch.zeros(F_, dtype=torch.long)
-        pending, final = [None] * F_, {}
-        for ctx in windows:
-            aud = audio_embeddings[:, ctx]
-            inp = (lat[:, :, ctx] * scale).float().repeat(2, 1, 1, 1, 1)
-            pred = unet_fn(inp, t, aud.reshape(-1, aud.shape[-2], aud.shape[-1]), kps_feature[:, :, ctx]).double()
-            u, cd = pred.chunk(2)
-            if guided[i]:
-                pred = u + guidance_scale * (cd - u)
-                if phi > 0.0:
-                    pred = rescale(pred, cd, phi)
-            else:
-                pred = cd
-            counter[ctx] += 1
-            pred = pred / count[ctx][None, None, :, None, None].double()
-            for li, fi in enumerate(ctx):
-                pending[fi] = pred[:, :, li].clone() if pending[fi] is None else pending[fi] + pred[:, :, li]
-                if counter[fi] == count[fi]:
-                    final[fi] = pending[fi]
-                    pending[fi] = None
-        x = lat.clone()
-        for fi, v in final.items():
-            if sampler == "dpm":
-                lat[:, :, fi], hist[:, :, fi] = D.update(sg, i, ords[i], x[:, :, fi], v, hist[:, :, fi])
-            elif sampler == "euler-a":
-                z = A.noise_like(seed, i, fi, c, h, w)[None]
-                lat[:, :, fi] = A.euler_a_update_ve(sg[i], sg[i + 1], x[:, :, fi], v, z)
-            else:
-                z = A.noise_like(seed, i, fi, c, h, w)[None] if sampler == "ddim-eta" else 0.0
-                a, ap = tab[i]
-                lat[:, :, fi] = A.ddim_eta_update(a, ap, eta if sampler == "ddim-eta" else 0.0, x[:, :, fi], v, z)
-    return lat

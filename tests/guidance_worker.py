@@ -1,6 +1,5 @@
 """One rank of tests/test_guidance_cpu.py's two-rank gloo run (TEST INFRASTRUCTURE): the small-config denoising loop
-(DDIM) with guidance_rescale and a guidance interval under emulated kernels (tests/fake_ops.py +
-guidance_restated.guidance_rescale)."""
+(DDIM) with guidance_rescale and a guidance interval under emulated kernels (loop_worker.emulate_kernels)."""
 import os
 import sys
 
@@ -25,15 +24,8 @@ def run(frame_shards=None, latent=8):
     return lat, dict(pipe.last_schedule), dict(pipe.last_guidance)
 
 
-def main(frame_shards=None, latent=8):
-    """Under RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT: this rank's final latents and its two schedules."""
-    import torch.distributed as dist
-    from v_express_amd import ops
+def main(rank, frame_shards=None, latent=8):
+    """One rank of loop_worker.spawn_gloo: this rank's final latents and its two schedules."""
     torch.set_num_threads(2)
-    dist.init_process_group("gloo")
     W.emulate_kernels()
-    ops.guidance_rescale = G.guidance_rescale
-    out = run(frame_shards, latent)
-    dist.barrier()
-    dist.destroy_process_group()
-    return out
+    return run(frame_shards, latent)

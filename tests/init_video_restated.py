@@ -1,14 +1,13 @@
 """float64 restatements of init-video sampling (TEST INFRASTRUCTURE) for tests/test_init_video_cpu.py and
 tests/test_gpu_init_video.py: the signal / noise pair (a_j, s_j) of every sampler's schedule level, the known-region blend
 of diffusers' StableDiffusionInpaintPipeline loop (`(1 - mask) * add_noise(init, noise, t_{i+1}) + mask * latents`, init
-itself after the last step) and the img2img start `add_noise(init, noise, t_b)`, the pixel composite, the mean-overlap loop
-of pipelines/v_express_pipeline.py:526-583 with all of it for every sampler, and emulated `ops.known_blend` /
-`ops.vae_postprocess_composite` in the style of tests/fake_ops.py."""
+itself after the last step) and the img2img start `add_noise(init, noise, t_b)`, the pixel composite, and emulated
+`ops.known_blend` / `ops.vae_postprocess_composite` in the style of tests/fake_ops.py.  The loop that uses them is
+tests/loop_restated.py."""
 import math
 
 import torch
 
-import ancestral_restated as A
 import dpm_restated as D
 
 KWARGS = D.KWARGS
@@ -84,70 +83,3 @@ def vae_postprocess_composite(x, n, c, h, w, init_video, mask, frame0=0):
     mk = mask.reshape(-1, h, w)
     mk = mk if mk.shape[0] == 1 else mk[frame0:frame0 + n]
     return composite(v, keep, mk).float().contiguous()
-
-
-def restated_loop(unet_fn, init, noise, m, windows, guidance_scale, kps_feature, audio_embeddings, n, strength,
-                  sampler="ddim", seed=None, eta=0.0, callback=None):
-    """pipelines/v_express_pipeline.py:526-583 in float64 with one update per frame per timestep (the textbook updates of
-    dpm_restated / ancestral_restated), started as diffusers' img2img pipelines start it - add_noise(init, noise, t_b),
-    b = begin_index(n, strength) - and, with a latent mask m [F, h * w] (1 = regenerate), blended after every step as
-    diffusers' inpaint loop blends it: the kept part is add_noise(init, noise, t_{i+1}), and init itself after the last
-    step.  Euler ancestral runs in its own (VE) frame, add_noise = init + sigma noise.  callback(i, latents) sees the
-    blended latents of step index i.  Returns the final latents (float64)."""
-    assert guidance_scale > 1.0
-    b = begin_index(n, strength)
-    init, noise = init.double(), noise.double()
-    _, c, F_, h, w = init.shape
-    sg = D.sigmas(n)
-    co = coefficients(sampler, n)
-    euler = sampler == "euler-a"
-
-    def known_at(j, last=False):
-        if last:
-            return init.clone()
-        if euler:
-            return init + sg[j] * noise
-        return co[j][0] * init + co[j][1] * noise
-    mm = None if m is None else m.double().reshape(1, 1, F_, h, w)
-    lat = known_at(b, last=b == n)
-    tab = A.ddim_table(n)
-    ords = D.orders(n, begin=b)
-    hist = torch.zeros_like(lat)
-    count = torch.zeros(F_, dtype=torch.long)
-    for ctx in windows:
-        count[ctx] += 1
-    ts = D.timesteps(n)
-    for i in range(b, n):
-        t = ts[i]
-        scale = 1.0 / math.sqrt(1.0 + sg[i] ** 2) if euler else 1.0
-        counter = torch.zeros(F_, dtype=torch.long)
-        pending, final = [None] * F_, {}
-        for ctx in windows:
-            aud = audio_embeddings[:, ctx]
-            inp = (lat[:, :, ctx] * scale).float().repeat(2, 1, 1, 1, 1)
-            pred = unet_fn(inp, t, aud.reshape(-1, aud.shape[-2], aud.shape[-1]), kps_feature[:, :, ctx]).double()
-            u, cd = pred.chunk(2)
-            pred = u + guidance_scale * (cd - u)
-            counter[ctx] += 1
-            pred = pred / count[ctx][None, None, :, None, None].double()
-            for li, fi in enumerate(ctx):
-                pending[fi] = pred[:, :, li].clone() if pending[fi] is None else pending[fi] + pred[:, :, li]
-                if counter[fi] == count[fi]:
-                    final[fi] = pending[fi]
-                    pending[fi] = None
-        x = lat.clone()
-        for fi, v in final.items():
-            if sampler == "dpm":
-                lat[:, :, fi], hist[:, :, fi] = D.update(sg, i, ords[i - b], x[:, :, fi], v, hist[:, :, fi])
-            elif euler:
-                z = A.noise_like(seed, i, fi, c, h, w)[None]
-                lat[:, :, fi] = A.euler_a_update_ve(sg[i], sg[i + 1], x[:, :, fi], v, z)
-            else:
-                z = A.noise_like(seed, i, fi, c, h, w)[None] if sampler == "ddim-eta" else 0.0
-                a, ap = tab[i]
-                lat[:, :, fi] = A.ddim_eta_update(a, ap, eta if sampler == "ddim-eta" else 0.0, x[:, :, fi], v, z)
-        if mm is not None:
-            lat = mm * lat + (1.0 - mm) * known_at(i + 1, last=i == n - 1)
-        if callback is not None:
-            callback(i, lat)
-    return lat

@@ -1,7 +1,7 @@
 """One rank of tests/test_init_video_cpu.py's two-rank gloo run (TEST INFRASTRUCTURE): VExpressPipeline.__call__ on the
-small configuration with init latents, a mask and strength < 1 under emulated kernels (tests/fake_ops.py +
-init_video_restated.known_blend).  No generator and no `latents` are passed: every rank draws its own noise from a
-differently seeded global generator, so the result is one process's only if rank 0's noise reaches every rank."""
+small configuration with init latents, a mask and strength < 1 under emulated kernels (loop_worker.emulate_kernels).
+No generator and no `latents` are passed: every rank draws its own noise from a differently seeded global generator, so
+the result is one process's only if rank 0's noise reaches every rank."""
 import os
 import sys
 
@@ -46,15 +46,8 @@ def run(frame_shards=None, latent=8, rank=0):
     return lat, dict(pipe.last_schedule), dict(pipe.last_init)
 
 
-def main(frame_shards=None, latent=8):
-    """Under RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT: this rank's final latents, its schedule and last_init."""
-    import torch.distributed as dist
-    from v_express_amd import ops
+def main(rank, frame_shards=None, latent=8):
+    """One rank of loop_worker.spawn_gloo: this rank's final latents, its schedule and last_init."""
     torch.set_num_threads(2)
-    dist.init_process_group("gloo")
     W.emulate_kernels()
-    ops.known_blend = R.known_blend
-    out = run(frame_shards, latent, dist.get_rank())
-    dist.barrier()
-    dist.destroy_process_group()
-    return out
+    return run(frame_shards, latent, rank)

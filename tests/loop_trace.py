@@ -1,5 +1,5 @@
 """Launch-trace recorder of the denoising loop (TEST INFRASTRUCTURE): runs `VExpressPipeline.__call__` on the small
-configuration under emulated kernels (tests/fake_ops.py + the *_restated.py stand-ins) and writes down, in order, every
+configuration under emulated kernels (loop_worker.emulate_kernels) and writes down, in order, every
 loop launch it issues - the `ops` wrappers of OPS, `unet.forward_tokens` and `dist.all_gather_units` - with the shape and
 dtype of every tensor argument, every int / bool / str / None / float argument, small int32 tensors (terms, frame ids,
 unit index) by value, and the four `last_*` reports of the call.  tests/test_loop_trace_cpu.py compares a fresh record
@@ -16,13 +16,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-import ancestral_restated as A  # noqa: E402
-import audio_guidance_restated as AG  # noqa: E402
 import cases  # noqa: E402
-import dpm_restated as D  # noqa: E402
-import guidance_restated as G  # noqa: E402
-import init_video_restated as R  # noqa: E402
-import window_blend_restated as WB  # noqa: E402
+import loop_worker  # noqa: E402
 
 OPS = ("gather_latents", "pack_rows", "combine_units", "combine_units3", "guidance_rescale", "guidance_rescale3",
        "overlap_blend", "overlap_ddim_step", "overlap_multistep_step", "overlap_ancestral_step", "known_blend")
@@ -50,19 +45,6 @@ CASES = {
 }
 
 
-def emulate(patch):
-    """loop_worker.emulate_kernels plus the stand-ins of the loop kernels tests/fake_ops.py does not have, all through
-    `patch.setattr` (a pytest monkeypatch, or anything with that method)."""
-    import loop_worker
-    ops = loop_worker.emulate_kernels(patch)
-    for name, fn in (("overlap_ancestral_step", A.overlap_ancestral_step), ("guidance_rescale", G.guidance_rescale),
-                     ("overlap_multistep_step", D.overlap_multistep_step), ("known_blend", R.known_blend),
-                     ("combine_units3", AG.combine_units3), ("guidance_rescale3", AG.guidance_rescale3),
-                     ("overlap_blend", WB.overlap_blend), ("_PADDED", {})):
-        patch.setattr(ops, name, fn)
-    return ops
-
-
 def describe(v):
     """One argument as JSON data."""
     if isinstance(v, torch.Tensor):
@@ -79,12 +61,6 @@ def describe(v):
     if isinstance(v, dict):
         return {str(k): describe(x) for k, x in v.items()}
     return dict(object=type(v).__name__)
-
-
-def _scheduler(kind):
-    from v_express_amd import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
-    return {"ddim": DDIMScheduler, "ddim-eta": DDIMScheduler, "dpm": DPMSolverMultistepScheduler,
-            "euler-a": EulerAncestralDiscreteScheduler}[kind](**G.KWARGS)
 
 
 def record_case(pipe, patch, name):
@@ -106,7 +82,7 @@ def record_case(pipe, patch, name):
         wrap(ops, op, op)
     wrap(pipe.denoising_unet, "forward_tokens", "unet.forward_tokens")
     wrap(pipe.dist, "all_gather_units", "dist.all_gather_units")
-    pipe.scheduler = _scheduler(sampler)
+    pipe.scheduler = loop_worker.scheduler(sampler)
     inp = synth.synthetic_inputs(cases.unet_cfg(cases.SMALL), F, LATENT, LATENT)
     rows = slice(0, 2) if s > 1.0 or (s_a is not None and s_a > 1.0) else slice(1, 2)    # one conditioning row
     kw = {}
@@ -139,16 +115,14 @@ def record_case(pipe, patch, name):
 
 def record(patch, pipe=None, names=None):
     """name -> record_case of every case, as it comes back from a JSON file (tuples are lists there)."""
-    import dist_gpu_worker as W
-    pipe = pipe or W.build_pipeline("cpu")
-    emulate(patch)
+    pipe = pipe or loop_worker.build_pipeline("cpu")
+    loop_worker.emulate_kernels(patch)
     out = {name: record_case(pipe, patch, name) for name in names or CASES}
     return json.loads(json.dumps(out))
 
 
 if __name__ == "__main__":
     torch.set_num_threads(4)
-    import loop_worker
     trace = record(loop_worker._Setattr)
     with open(sys.argv[1], "w") as fh:
         json.dump(trace, fh, separators=(",", ":"))

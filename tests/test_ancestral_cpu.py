@@ -3,22 +3,17 @@ coefficients of DDIMScheduler.ancestral_coefficients (eta > 0) and EulerAncestra
 textbook updates in float64, Euler ancestral against DDIM eta = 1, the analytic model, the options, and
 VExpressPipeline.__call__ with the ancestral update under emulated kernels (one process and two gloo ranks)."""
 import math
-import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 import ancestral_restated as A
 import cases
 import dpm_restated as D
-
-
-def rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
+from loop_restated import restated_loop
+from loop_worker import (SEED, call_pipeline as _call, emulated, inputs, oracle_unet, rel_l2,  # noqa: F401
+                         small_pipe, spawn_gloo)
 
 
 def ddim(**kw):
@@ -240,47 +235,14 @@ def test_eta_limits():
 
 
 # ------------------------------------------------------------------------------------------------ (6) __call__
-@pytest.fixture()
-def emulated(monkeypatch):
-    import fake_ops
-    from v_express_amd import ops, prologue, unet_3d, vae
-    fake_ops.install(monkeypatch, ops)
-    monkeypatch.setattr(ops, "overlap_ancestral_step", A.overlap_ancestral_step)
-    monkeypatch.setattr(unet_3d._UNetBase, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(vae.AutoencoderKLDecoder, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(prologue._Module, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(ops, "_PADDED", {})
-    return ops
-
-
-@pytest.fixture(scope="module")
-def small_pipe():
-    import dist_gpu_worker as W
-    return W.build_pipeline("cpu")
-
-
-def _call(pipe, scheduler, inp, F_, steps, cf, co, **kw):
-    pipe.scheduler = scheduler
-    kw.setdefault("latents", inp["latents"])
-    return pipe(None, None, None, 64, 64, F_, steps, cases.GUIDANCE, context_frames=cf, context_overlap=co,
-                reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD,
-                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
-                audio_embeddings=inp["audio_embeddings"], decode=False, **kw)
-
-
-SEED = (0x9E3779B9 << 32) | 0x7F4A7C15
-
-
 @pytest.mark.parametrize("sampler", ["ddim-0.5", "ddim-1", "euler-a"])
 def test_pipeline_call_ancestral_vs_restated_oracle_loop(emulated, small_pipe, sampler):
     """__call__ (reflected last window [8, 9, 10, 9], 5 steps) under emulated kernels against the per-frame restated loop
     over the oracle UNet with the restated noise; units_per_call 2 and 4 give the same bits."""
-    from oracle import loop as OL, unet as OU
-    from v_express_amd import synth
+    from oracle import loop as OL
     F_, cf, co, _ = cases.PIPELINE_CASES["reflected_F11_c4o2"]
     steps = 5
-    cfg, ocfg = cases.unet_cfg(cases.SMALL), cases.oracle_cfg(cases.SMALL)
-    inp = synth.synthetic_inputs(cfg, F_, 8, 8)
+    inp = inputs(F_)
     eta = {"ddim-0.5": 0.5, "ddim-1": 1.0, "euler-a": 0.0}[sampler]
     sched = euler() if sampler == "euler-a" else ddim()
     calls = []
@@ -301,14 +263,10 @@ def test_pipeline_call_ancestral_vs_restated_oracle_loop(emulated, small_pipe, s
         small_pipe.units_per_call = 2
     got = runs[2]
     assert calls == list(range(steps)) * 2 and torch.equal(runs[2], runs[4])
-    sd3, sd2 = synth.unet3d_state_dict(cfg), synth.refnet_state_dict(cfg)
     with torch.no_grad():
-        banks = OU.reader_banks(OU.refnet_banks(sd2, ocfg, inp["ref_latents"]))
-        ref = A.restated_loop(lambda x, t, e, k: OU.unet3d_forward(sd3, ocfg, x, t, e, k, banks, cases.W_REF,
-                                                                   cases.W_AUD),
-                              inp["latents"], OL.uniform_windows(F_, cf, co), cases.GUIDANCE, inp["kps_features"],
-                              inp["audio_embeddings"], steps, "euler-a" if sampler == "euler-a" else "ddim-eta",
-                              SEED, eta)
+        ref = restated_loop(oracle_unet(inp), inp["latents"], OL.uniform_windows(F_, cf, co), cases.GUIDANCE,
+                            inp["kps_features"], inp["audio_embeddings"], steps,
+                            "euler-a" if sampler == "euler-a" else "ddim-eta", seed=SEED, eta=eta)
     r = rel_l2(got, ref)
     print(f"[__call__ {sampler}, emulated kernels, reflected_F11_c4o2, {steps} steps] relL2 vs restated loop {r:.4g}")
     assert torch.isfinite(got).all() and r <= 5e-2
@@ -396,28 +354,10 @@ def test_eta_with_other_schedulers_and_bad_eta_fail_before_any_kernel(emulated, 
                            [[0, 1, 2, 3]], cases.GUIDANCE)
 
 
-def _worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    import ancestral_worker
-    q.put((rank, ancestral_worker.main().numpy().copy()))      # by value (see test_host_emulated._worker)
-
-
 def test_two_gloo_ranks_with_euler_ancestral_are_bit_identical_to_one_process(emulated):
     """The noise depends on (seed, step, frame, channel, pixel) only: the clip of two gloo ranks (the windows of F = 14,
     8 / 2 split over them) is bit-identical to one process, on both ranks."""
     import ancestral_worker
     ref = ancestral_worker.run()
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    results = [(r, torch.from_numpy(a)) for r, a in (q.get(timeout=600) for _ in procs)]
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    for rank, lat in results:
+    for rank, lat in enumerate(spawn_gloo(ancestral_worker.main, 2, timeout=600)):
         assert torch.isfinite(lat).all() and torch.equal(lat, ref), (rank, rel_l2(lat, ref))

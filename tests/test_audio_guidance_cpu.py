@@ -5,92 +5,17 @@ guidance_scale <= 1, the defaults bit for bit, an all-zero audio row, every samp
 interval, init-video sampling, the argument errors (the C entry points' included), the unit schedules for three rows and
 two gloo ranks against one process."""
 import ctypes
-import os
-import socket
-
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import ancestral_restated as A
 import audio_guidance_restated as AG
 import cases
-import dpm_restated as D
-import guidance_restated as G
-import init_video_restated as R
+from loop_restated import restated_loop
+from loop_worker import (SEED, call_pipeline as _call, emulated, inputs as _inputs,  # noqa: F401
+                         oracle_unet as _oracle_unet, rel_l2, scheduler, small_pipe, spawn_gloo, trace_ops as _trace)
 
-SEED = (0x9E3779B9 << 32) | 0x7F4A7C15
 PHI, S, S_A = 0.7, cases.GUIDANCE, 6.0
 BOUND = 5e-2        # the relative-L2 bound tests/test_guidance_cpu.py applies to the two-row loop at these geometries
-LOOP_OPS = ("gather_latents", "pack_rows", "combine_units", "guidance_rescale", "combine_units3", "guidance_rescale3",
-            "overlap_ddim_step", "overlap_multistep_step", "overlap_ancestral_step", "known_blend")
-
-
-def rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
-
-
-@pytest.fixture()
-def emulated(monkeypatch):
-    import fake_ops
-    from v_express_amd import ops, prologue, unet_3d, vae
-    fake_ops.install(monkeypatch, ops)
-    monkeypatch.setattr(ops, "overlap_ancestral_step", A.overlap_ancestral_step)
-    monkeypatch.setattr(ops, "overlap_multistep_step", D.overlap_multistep_step)
-    monkeypatch.setattr(ops, "guidance_rescale", G.guidance_rescale)
-    monkeypatch.setattr(ops, "known_blend", R.known_blend)
-    monkeypatch.setattr(ops, "combine_units3", AG.combine_units3)
-    monkeypatch.setattr(ops, "guidance_rescale3", AG.guidance_rescale3)
-    monkeypatch.setattr(unet_3d._UNetBase, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(vae.AutoencoderKLDecoder, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(prologue._Module, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(ops, "_PADDED", {})
-    return ops
-
-
-@pytest.fixture(scope="module")
-def small_pipe():
-    import dist_gpu_worker as W
-    return W.build_pipeline("cpu")
-
-
-def scheduler(kind):
-    from v_express_amd import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
-    return {"ddim": DDIMScheduler, "ddim-eta": DDIMScheduler, "dpm": DPMSolverMultistepScheduler,
-            "euler-a": EulerAncestralDiscreteScheduler}[kind](**G.KWARGS)
-
-
-def _call(pipe, sched, inp, F_, steps, cf, co, guidance=S, **kw):
-    pipe.scheduler = sched
-    kw.setdefault("latents", inp["latents"])
-    return pipe(None, None, None, 64, 64, F_, steps, guidance, context_frames=cf, context_overlap=co,
-                reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD,
-                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
-                audio_embeddings=inp["audio_embeddings"], decode=False, **kw)
-
-
-def _inputs(F_):
-    from v_express_amd import synth
-    return synth.synthetic_inputs(cases.unet_cfg(cases.SMALL), F_, 8, 8)
-
-
-def _oracle_unet(inp):
-    from v_express_amd import synth
-    cfg, ocfg = cases.unet_cfg(cases.SMALL), cases.oracle_cfg(cases.SMALL)
-    return AG.oracle_rows_unet(synth.unet3d_state_dict(cfg), synth.refnet_state_dict(cfg), ocfg, inp["ref_latents"],
-                               cases.W_REF, cases.W_AUD)
-
-
-def _trace(monkeypatch, ops, names=LOOP_OPS):
-    """Records the names of the loop's ops as they are called."""
-    trace = []
-    for name in names:
-        def wrap(*a, _fn=getattr(ops, name), _name=name, **k):
-            trace.append(_name)
-            return _fn(*a, **k)
-        monkeypatch.setattr(ops, name, wrap)
-    return trace
 
 
 # ------------------------------------------------------------------------------------------------ (1) three rows
@@ -124,8 +49,8 @@ def test_audio_scale_changes_the_clip_and_matches_the_restatement(emulated, smal
     assert trace.count("combine_units3") == steps and "combine_units" not in trace and "guidance_rescale3" not in trace
     assert torch.isfinite(got).all() and rel_l2(got, plain) > 1e-3
     with torch.no_grad():
-        ref = AG.restated_loop(_oracle_unet(inp), inp["latents"], windows, S, S_A, inp["kps_features"],
-                               inp["audio_embeddings"], steps, "ddim")
+        ref = restated_loop(_oracle_unet(inp), inp["latents"], windows, S, inp["kps_features"], inp["audio_embeddings"],
+                            steps, "ddim", s_a=S_A)
     r, r2 = rel_l2(got, ref), rel_l2(plain, ref)
     print(f"[__call__ audio_guidance_scale={S_A}, guidance_scale={S}, emulated kernels, {steps} steps] relL2 vs restated "
           f"three-row loop {r:.4g}; the two-row clip {r2:.4g}")
@@ -218,8 +143,8 @@ def test_audio_scale_alone_runs_the_rows_m_c_through_the_two_row_ops(emulated, s
     # both windows in one call of 4 rows: every row reads the reference bank, the m rows carry zero audio
     assert calls == [([1, 1, 1, 1], [True, False, True, False])] * steps
     with torch.no_grad():
-        ref = AG.restated_loop(_oracle_unet(inp), inp["latents"], OL.uniform_windows(F_, cf, co), 1.0, 3.5,
-                               inp["kps_features"], inp["audio_embeddings"], steps, "ddim")
+        ref = restated_loop(_oracle_unet(inp), inp["latents"], OL.uniform_windows(F_, cf, co), 1.0, inp["kps_features"],
+                            inp["audio_embeddings"], steps, "ddim", s_a=3.5)
     nocfg = _call(small_pipe, scheduler("ddim"), cases.cond_only(inp), F_, steps, cf, co, guidance=1.0)
     r, r2 = rel_l2(got, ref), rel_l2(nocfg, ref)
     print(f"[__call__ guidance_scale=1, audio_guidance_scale=3.5, {steps} steps] relL2 vs restated (m, c) loop {r:.4g}; "
@@ -308,9 +233,8 @@ def test_every_sampler_with_rescale_and_interval_vs_restated_loop(emulated, smal
     assert ("unet", (1, 1, 1, 1), (False,) * 4) in full[cut3:] and ("unet", (1,), (False,)) in full[cut3:]
     assert full[:cut3].count("guidance_rescale3") == 3 and "combine_units" not in full[:cut3]
     with torch.no_grad():
-        ref = AG.restated_loop(_oracle_unet(inp), inp["latents"], OL.uniform_windows(F_, cf, co), S, S_A,
-                               inp["kps_features"], inp["audio_embeddings"], steps, kind, phi=PHI, end=0.6, seed=SEED,
-                               eta=eta)
+        ref = restated_loop(_oracle_unet(inp), inp["latents"], OL.uniform_windows(F_, cf, co), S, inp["kps_features"],
+                            inp["audio_embeddings"], steps, kind, s_a=S_A, phi=PHI, end=0.6, seed=SEED, eta=eta)
     r = rel_l2(got, ref)
     print(f"[__call__ {kind}, audio scale {S_A}, rescale {PHI}, guidance_end 0.6, reflected_F11_c4o2, {steps} steps] "
           f"relL2 vs restated loop {r:.4g}")
@@ -457,33 +381,14 @@ def test_unit_schedules_for_three_rows(world):
             assert max(whole) == min(whole) and sorted(sum(mixed.whole, []) + mixed.split) == units
 
 
-def _worker(rank, world, port, q, geometry):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    import audio_guidance_worker
-    lat, sched, guid = audio_guidance_worker.main(geometry)
-    q.put((rank, lat.numpy().copy(), sched, guid))             # by value (see test_host_emulated._worker)
-
-
 @pytest.mark.parametrize("geometry,units", [("one_window", 3), ("two_windows", 6)])
 def test_two_gloo_ranks_are_bit_identical_to_one_process(emulated, geometry, units):
     """Three rows per window, the rescale and an interval on two gloo ranks (whole units): one window = 3 units, ranks
     (u, m) | (c), so the c row runs alone on its rank; two windows = 6 units.  The bits of one process, on both ranks."""
     import audio_guidance_worker
     ref, _, _ = audio_guidance_worker.run(geometry)
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q, geometry)) for r in range(2)]
-    for p in procs:
-        p.start()
-    results = [q.get(timeout=900) for _ in procs]
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    for rank, lat, sched, guid in results:
-        lat = torch.from_numpy(lat)
+    results = spawn_gloo(audio_guidance_worker.main, 2, geometry, timeout=900)
+    for rank, (lat, sched, guid) in enumerate(results):
         assert torch.isfinite(lat).all() and torch.equal(lat, ref), (rank, rel_l2(lat, ref))
         assert sched == dict(kind="whole units", frame_shards=1, mixed_shards=1, units=units, world=2)
         assert guid["unguided_schedule"]["units"] == units // 3 and guid["guided_steps"] == 2

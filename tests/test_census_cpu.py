@@ -5,11 +5,11 @@ one GEMM signature scaled by 1 + 2^-4) the census flags exactly that signature, 
 model-level golden bound of test_unet_forward_host_composition_vs_reference_golden (relative L2 <= 3e-2)."""
 import os
 
-import pytest
 import torch
 
 import cases
 import census
+from loop_worker import emulated  # noqa: F401
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -17,18 +17,6 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 def rel_l2(a, b):
     a, b = a.float(), b.float()
     return ((a - b).norm() / (b.norm() + 1e-12)).item()
-
-
-@pytest.fixture()
-def emulated(monkeypatch):
-    import fake_ops
-    from v_express_amd import ops, prologue, unet_3d, vae
-    fake_ops.install(monkeypatch, ops)
-    monkeypatch.setattr(unet_3d._UNetBase, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(vae.AutoencoderKLDecoder, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(prologue._Module, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(ops, "_PADDED", {})
-    return ops
 
 
 def _forward(cen):

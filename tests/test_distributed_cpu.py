@@ -1,13 +1,10 @@
 """world_size=2 `gloo` test (CPU) of the window x CFG-half sharding: every rank computes only its units, one
 all-gather per timestep, redundant combine + DDIM on every rank -> bit-identical to the single-process loop."""
-import os
-import socket
-
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
+from loop_worker import spawn_gloo
 from oracle import loop as OL
 from v_express_amd import context, distributed
 from v_express_amd.scheduler import DDIMScheduler
@@ -73,9 +70,7 @@ def run_loop(rank, world, F, cs, co, steps, dc, S=1):
     return lat
 
 
-def _worker(rank, world, port, F, cs, co, steps, q, S=1):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _worker(rank, world, F, cs, co, steps, S=1):
     dc = distributed.DistContext.from_env()
     assert dc.enabled and dc.world_size == world and dc.rank == rank
     out = run_loop(rank, world, F, cs, co, steps, dc, S)
@@ -83,51 +78,22 @@ def _worker(rank, world, port, F, cs, co, steps, q, S=1):
     frames = torch.zeros(distributed.split_frames(F, world)[0][1], 3)
     frames[:hi - lo] = float(rank + 1)
     allf = dc.all_gather_frames(frames).reshape(-1, 3)[:F]
-    # by VALUE (numpy arrays are pickled into the queue): a torch tensor travels as a file descriptor that the parent must
-    # fetch from THIS process while it is still alive - on a busy machine the child was gone first (EOFError in q.get)
-    q.put((rank, out.numpy().copy(), allf[:, 0].numpy().copy()))
-    dist.barrier()
-    dist.destroy_process_group()
+    return out, allf[:, 0]
 
 
 @pytest.mark.parametrize("F,cs,co", [(28, 8, 2), (11, 4, 2)])
 def test_sharded_loop_is_bit_identical_to_single_process(F, cs, co):
     steps, world = 3, 2
     ref = run_loop(0, 1, F, cs, co, steps, distributed.DistContext())
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, F, cs, co, steps, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = [q.get(timeout=120) for _ in procs]
-    results = [(r, torch.from_numpy(o), torch.from_numpy(w)) for r, o, w in results]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    for rank, out, owner in results:
+    for rank, (out, owner) in enumerate(spawn_gloo(_worker, world, world, F, cs, co, steps, timeout=120, join=60)):
         assert torch.equal(out, ref), f"rank {rank} diverged from the single-process loop"
         lo, hi = distributed.split_frames(F, world)[0]
         assert (owner[:hi] == 1).all() and (owner[hi:] == 2).all()
 
 
 def _spawn(world, F, cs, co, steps, S):
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, F, cs, co, steps, q, S)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = [q.get(timeout=180) for _ in procs]
-    results = [(r, torch.from_numpy(o), torch.from_numpy(w)) for r, o, w in results]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    return results
+    results = spawn_gloo(_worker, world, world, F, cs, co, steps, S, timeout=180, join=60)
+    return [(rank, out, owner) for rank, (out, owner) in enumerate(results)]
 
 
 @pytest.mark.parametrize("world,S,F,cs,co", [(2, 2, 8, 8, 2), (4, 2, 8, 8, 2), (4, 2, 14, 8, 2), (4, 4, 8, 8, 2),
@@ -253,9 +219,7 @@ def test_subgroup_creation_order_is_identical_on_every_rank_at_world_8(monkeypat
         assert list(first) == want
 
 
-def _worker_groups8(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _worker_groups8(rank):
     dc = distributed.DistContext.from_env()
     got = []
     with distributed.CommTimer() as ct:
@@ -269,9 +233,7 @@ def _worker_groups8(rank, world, port, q):
             back = fs.to_frame_shard(px, b, f_loc)
             got.append((S, torch.equal(back, x), tuple(px.shape)))
         gathered = dc.all_gather_units(torch.full((2, 4), float(rank)), 2)
-    q.put((rank, got, gathered[:, 0, 0].tolist(), {k: v["calls"] for k, v in ct.summary().items()}))
-    dist.barrier()
-    dist.destroy_process_group()
+    return got, gathered[:, 0, 0].tolist(), {k: v["calls"] for k, v in ct.summary().items()}
 
 
 def test_world_8_sub_groups_and_exchanges_over_gloo():
@@ -279,20 +241,9 @@ def test_world_8_sub_groups_and_exchanges_over_gloo():
     pipeline uses, a layout round trip through each group's all-to-all, the world-wide all-gather, and CommTimer's
     bookkeeping (what bench.py --gpus N reports as the collectives' share of a step)."""
     world = 8
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker_groups8, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = [q.get(timeout=240) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    assert sorted(r for r, *_ in results) == list(range(world))
-    for rank, got, owners, calls in results:
+    results = spawn_gloo(_worker_groups8, world, timeout=240, join=60)
+    assert len(results) == world
+    for rank, (got, owners, calls) in enumerate(results):
         assert got == [(2, True, (2 * 8, 4, 3)), (4, True, (2 * 8, 2, 3))], (rank, got)
         assert owners == [float(r) for r in range(world)]
         assert calls == {"all_to_all": 4, "all_gather": 1}, calls

@@ -3,21 +3,15 @@ coefficients against float64 restatements (tests/dpm_restated.py), the stateful 
 mean-overlap loop, convergence on an analytic model against DDIM, and VExpressPipeline.__call__ with the DPM-Solver++
 update under emulated kernels (one process and two gloo ranks)."""
 import math
-import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 import cases
 import dpm_restated as D
-
-
-def rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
+from loop_restated import restated_loop
+from loop_worker import call_pipeline, emulated, inputs, oracle_unet, rel_l2, spawn_gloo  # noqa: F401
 
 
 def make(**kw):
@@ -170,8 +164,8 @@ def test_stateful_step_in_the_oracle_single_window_loop():
             return s.step(v, t, x).prev_sample
     got = OL.mean_overlap(unet_fn, lat, s.timesteps.tolist(), Stepper(), windows, cases.GUIDANCE,
                           torch.zeros(2, 1, F_, 8, 8), torch.zeros(2, F_, 1, 8))
-    ref = D.restated_loop(unet_fn, lat, windows, cases.GUIDANCE, torch.zeros(2, 1, F_, 8, 8),
-                          torch.zeros(2, F_, 1, 8), n)
+    ref = restated_loop(lambda x, t, e, k, rows: unet_fn(x, t, e, k), lat, windows, cases.GUIDANCE,
+                        torch.zeros(2, 1, F_, 8, 8), torch.zeros(2, F_, 1, 8), n, "dpm")
     r = rel_l2(got, ref)
     print(f"[stateful step, single window, {n} steps] relL2 vs float64 = {r:.3g}")
     assert torch.isfinite(got).all() and r <= 1e-5
@@ -221,42 +215,19 @@ def test_convergence_on_the_analytic_model():
 
 
 # ------------------------------------------------------------------------------------------------ (d) __call__
-@pytest.fixture()
-def emulated(monkeypatch):
-    import fake_ops
-    from v_express_amd import ops, prologue, unet_3d, vae
-    fake_ops.install(monkeypatch, ops)
-    monkeypatch.setattr(ops, "overlap_multistep_step", D.overlap_multistep_step)
-    monkeypatch.setattr(unet_3d._UNetBase, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(vae.AutoencoderKLDecoder, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(prologue._Module, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(ops, "_PADDED", {})
-    return ops
-
-
-def _small_pipe(scheduler):
-    import dist_gpu_worker as W
-    pipe = W.build_pipeline("cpu")
-    pipe.scheduler = scheduler
-    return pipe
-
-
-def _call(pipe, inp, F_, steps, cf, co):
-    return pipe(None, None, None, 64, 64, F_, steps, cases.GUIDANCE, context_frames=cf, context_overlap=co,
-                reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD,
-                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
-                audio_embeddings=inp["audio_embeddings"], latents=inp["latents"], decode=False)
+def _call(scheduler, inp, F_, steps, cf, co):
+    """On a pipeline of its own."""
+    import loop_worker
+    return call_pipeline(loop_worker.build_pipeline("cpu"), scheduler, inp, F_, steps, cf, co)
 
 
 def test_pipeline_call_with_dpm_solver_vs_restated_oracle_loop(emulated):
     """__call__ with DPM++ 2M (5 steps, reflected last window [8, 9, 10, 9]) under emulated kernels against the per-frame
     restated loop over the oracle UNet; the DDIM clip of the same inputs differs from it (the update really changed)."""
-    from oracle import loop as OL, unet as OU
-    from v_express_amd import synth
+    from oracle import loop as OL
     F_, cf, co, _ = cases.PIPELINE_CASES["reflected_F11_c4o2"]
     steps = 5
-    cfg, ocfg = cases.unet_cfg(cases.SMALL), cases.oracle_cfg(cases.SMALL)
-    inp = synth.synthetic_inputs(cfg, F_, 8, 8)
+    inp = inputs(F_)
     calls = []
     orig = emulated.overlap_multistep_step
 
@@ -264,17 +235,13 @@ def test_pipeline_call_with_dpm_solver_vs_restated_oracle_loop(emulated):
         calls.append(a[-1])
         return orig(*a)
     emulated.overlap_multistep_step = counted
-    got = _call(_small_pipe(make()), inp, F_, steps, cf, co)
+    got = _call(make(), inp, F_, steps, cf, co)
     assert len(calls) == steps and calls[-1][2:] == (0.0, -1.0, 0.0)
-    sd3, sd2 = synth.unet3d_state_dict(cfg), synth.refnet_state_dict(cfg)
     with torch.no_grad():
-        banks = OU.reader_banks(OU.refnet_banks(sd2, ocfg, inp["ref_latents"]))
-        ref = D.restated_loop(lambda x, t, e, k: OU.unet3d_forward(sd3, ocfg, x, t, e, k, banks, cases.W_REF,
-                                                                   cases.W_AUD),
-                              inp["latents"], OL.uniform_windows(F_, cf, co), cases.GUIDANCE, inp["kps_features"],
-                              inp["audio_embeddings"], steps)
+        ref = restated_loop(oracle_unet(inp), inp["latents"], OL.uniform_windows(F_, cf, co), cases.GUIDANCE,
+                            inp["kps_features"], inp["audio_embeddings"], steps, "dpm")
     from v_express_amd import DDIMScheduler
-    ddim = _call(_small_pipe(DDIMScheduler(**D.KWARGS)), inp, F_, steps, cf, co)
+    ddim = _call(DDIMScheduler(**D.KWARGS), inp, F_, steps, cf, co)
     r, rd = rel_l2(got, ref), rel_l2(ddim, ref)
     print(f"[__call__ DPM++ 2M, emulated kernels, reflected_F11_c4o2, {steps} steps] relL2 vs restated oracle loop "
           f"{r:.4g} (the DDIM clip: {rd:.4g})")
@@ -282,7 +249,7 @@ def test_pipeline_call_with_dpm_solver_vs_restated_oracle_loop(emulated):
 
 
 def test_unsupported_scheduler_fails_before_any_kernel(emulated, monkeypatch):
-    from v_express_amd import synth
+    import loop_worker
 
     class Other:
         init_noise_sigma = 1.0
@@ -295,18 +262,12 @@ def test_unsupported_scheduler_fails_before_any_kernel(emulated, monkeypatch):
     for name in ("gather_latents", "combine_units", "overlap_ddim_step", "overlap_multistep_step", "ncfhw_to_nhwc",
                  "groupnorm", "gemm"):
         monkeypatch.setattr(emulated, name, no_kernels)
-    pipe = _small_pipe(Other())
-    inp = synth.synthetic_inputs(cases.unet_cfg(cases.SMALL), 4, 8, 8)
+    pipe = loop_worker.build_pipeline("cpu")
+    inp = inputs(4)
     with pytest.raises(TypeError, match="DDIMScheduler or .*DPMSolverMultistepScheduler"):
-        _call(pipe, inp, 4, 2, 4, 2)
+        call_pipeline(pipe, Other(), inp, 4, 2, 4, 2)
     with pytest.raises(TypeError, match="DPMSolverMultistepScheduler"):
         pipe.denoise(inp["latents"].clone(), None, None, [999], [[0, 1, 2, 3]], cases.GUIDANCE)
-
-
-def _dpm_worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    import dpm_worker
-    q.put((rank, dpm_worker.main().numpy().copy()))      # by value (see test_host_emulated._worker)
 
 
 def test_two_gloo_ranks_with_dpm_solver_are_bit_identical_to_one_process(emulated):
@@ -314,17 +275,5 @@ def test_two_gloo_ranks_with_dpm_solver_are_bit_identical_to_one_process(emulate
     ranks (the windows of F = 14, 8 / 2 split over them) is bit-identical to one process, on both ranks."""
     import dpm_worker
     ref = dpm_worker.run()
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_dpm_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    results = [(r, torch.from_numpy(a)) for r, a in (q.get(timeout=600) for _ in procs)]
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    for rank, lat in results:
+    for rank, lat in enumerate(spawn_gloo(dpm_worker.main, 2, timeout=600)):
         assert torch.isfinite(lat).all() and torch.equal(lat, ref), (rank, rel_l2(lat, ref))

@@ -9,20 +9,12 @@ import torch
 
 import ancestral_restated as A
 import cases
+from loop_restated import restated_loop
+from loop_worker import call_small as _call, cosine, dev, oracle_on_cpu, rel_l2, small  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SEEDS = (0, 12345, (0xDEADBEEF << 32) | 0x01234567)
-
-
-def rel_l2(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
-
-
-def cosine(a, b):
-    a, b = a.double().cpu().flatten(), b.double().cpu().flatten()
-    return (a @ b / (a.norm() * b.norm() + 1e-30)).item()
 
 
 def check(got, ref, what, rel, mx):
@@ -33,14 +25,6 @@ def check(got, ref, what, rel, mx):
     r = rel_l2(got, ref)
     assert err.max().item() <= mx * ref.abs().max().item() + 1e-5 and r <= rel, \
         f"{what}: max|err|={err.max().item():.4g}, relL2={r:.3g}"
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    torch.cuda.set_device(0)
-    return "cuda"
 
 
 def plan_args(windows, F_, dev):
@@ -157,25 +141,6 @@ def test_noise_statistics_at_the_configs1_shape(dev):
 
 
 # ------------------------------------------------------------------------------------------------ (4) pipeline
-@pytest.fixture(scope="module")
-def small(dev):
-    import dist_gpu_worker as W
-    from v_express_amd import synth
-    F_, cf, co, _ = cases.PIPELINE_CASES["reflected_F11_c4o2"]
-    cfg = cases.unet_cfg(cases.SMALL)
-    return dict(pipe=W.build_pipeline(dev), inp=synth.synthetic_inputs(cfg, F_, 8, 8), F=F_, cf=cf, co=co,
-                sd3=synth.unet3d_state_dict(cfg), sd2=synth.refnet_state_dict(cfg))
-
-
-def _call(S, scheduler, steps, **kw):
-    pipe, inp = S["pipe"], S["inp"]
-    pipe.scheduler = scheduler
-    return pipe(None, None, None, 64, 64, S["F"], steps, cases.GUIDANCE, context_frames=S["cf"],
-                context_overlap=S["co"], reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD,
-                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
-                audio_embeddings=inp["audio_embeddings"], latents=inp["latents"], decode=False, **kw).cpu()
-
-
 def _sched(sampler):
     from v_express_amd import DDIMScheduler, EulerAncestralDiscreteScheduler
     return (EulerAncestralDiscreteScheduler if sampler == "euler-a" else DDIMScheduler)(**A.KWARGS)
@@ -183,27 +148,18 @@ def _sched(sampler):
 
 @pytest.mark.parametrize("sampler", ["ddim-eta", "euler-a"])
 def test_pipeline_ancestral_vs_restated_oracle_loop(small, sampler):
-    from oracle import loop as OL, unet as OU
+    from oracle import loop as OL
     steps, seed = 6, SEEDS[2]
     eta = 1.0 if sampler == "ddim-eta" else 0.0
     got = _call(small, _sched(sampler), steps, eta=eta, noise_seed=seed)
     again = _call(small, _sched(sampler), steps, eta=eta, noise_seed=seed)
     other = _call(small, _sched(sampler), steps, eta=eta, noise_seed=seed + 1)
     assert torch.equal(got, again) and rel_l2(other, got) > 1e-2
-    ocfg = cases.oracle_cfg(cases.SMALL)
     inp = small["inp"]
-    nthreads = torch.get_num_threads()
-    torch.set_num_threads(min(16, nthreads))
-    try:
-        with torch.no_grad():
-            banks = OU.reader_banks(OU.refnet_banks(small["sd2"], ocfg, inp["ref_latents"]))
-            ref = A.restated_loop(lambda x, t, e, k: OU.unet3d_forward(small["sd3"], ocfg, x, t, e, k, banks,
-                                                                       cases.W_REF, cases.W_AUD),
-                                  inp["latents"], OL.uniform_windows(small["F"], small["cf"], small["co"]),
-                                  cases.GUIDANCE, inp["kps_features"], inp["audio_embeddings"], steps, sampler, seed,
-                                  eta)
-    finally:
-        torch.set_num_threads(nthreads)
+    with oracle_on_cpu():
+        ref = restated_loop(small["oracle"], inp["latents"], OL.uniform_windows(small["F"], small["cf"], small["co"]),
+                            cases.GUIDANCE, inp["kps_features"], inp["audio_embeddings"], steps, sampler, seed=seed,
+                            eta=eta)
     r, c = rel_l2(got, ref), cosine(got, ref)
     print(f"[{sampler}, SMALL, reflected_F11_c4o2, {steps} steps] relL2={r:.4g} cosine={c:.6f} vs the restated loop")
     assert torch.isfinite(got).all() and r <= 5e-2 and c >= 0.998, (r, c)

@@ -9,29 +9,12 @@ import torch
 
 import audio_guidance_restated as AG
 import cases
-import guidance_restated as G
+from loop_restated import restated_loop
+from loop_worker import call_small, cosine, dev, oracle_on_cpu, rel_l2, scheduler, small  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 S, S_A, PHI = 3.5, 6.0, 0.7
-
-
-def rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
-
-
-def cosine(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return (a @ b / (a.norm() * b.norm())).item()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    torch.cuda.set_device(0)
-    return "cuda"
 
 
 def predictions(nW, c, f, hw, mean, seed):
@@ -167,41 +150,16 @@ def test_equal_c_and_m_rows_give_the_two_row_kernel(dev, elem, s_a):
 
 
 # ------------------------------------------------------------------------------------------------ (13) the pipeline
-@pytest.fixture(scope="module")
-def small(dev):
-    import dist_gpu_worker as W
-    from v_express_amd import synth
-    F_, cf, co, _ = cases.PIPELINE_CASES["reflected_F11_c4o2"]
-    cfg = cases.unet_cfg(cases.SMALL)
-    inp = synth.synthetic_inputs(cfg, F_, 8, 8)
-    return dict(pipe=W.build_pipeline(dev), inp=inp, F=F_, cf=cf, co=co,
-                oracle=AG.oracle_rows_unet(synth.unet3d_state_dict(cfg), synth.refnet_state_dict(cfg),
-                                           cases.oracle_cfg(cases.SMALL), inp["ref_latents"], cases.W_REF, cases.W_AUD))
-
-
-def _call(S_, steps, inp=None, guidance=cases.GUIDANCE, **kw):
-    from v_express_amd import DDIMScheduler
-    pipe, inp = S_["pipe"], inp or S_["inp"]
-    pipe.scheduler = DDIMScheduler(**G.KWARGS)
-    kw.setdefault("latents", inp["latents"])
-    return pipe(None, None, None, 64, 64, S_["F"], steps, guidance, context_frames=S_["cf"],
-                context_overlap=S_["co"], reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD,
-                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
-                audio_embeddings=inp["audio_embeddings"], decode=False, **kw).cpu()
+def _call(S_, steps, **kw):
+    return call_small(S_, scheduler("ddim"), steps, **kw)
 
 
 def _restated(small, steps, s, s_a, **kw):
     from oracle import loop as OL
     inp = small["inp"]
-    nthreads = torch.get_num_threads()
-    torch.set_num_threads(min(16, nthreads))
-    try:
-        with torch.no_grad():
-            return AG.restated_loop(small["oracle"], inp["latents"], OL.uniform_windows(small["F"], small["cf"],
-                                                                                        small["co"]),
-                                    s, s_a, inp["kps_features"], inp["audio_embeddings"], steps, "ddim", **kw)
-    finally:
-        torch.set_num_threads(nthreads)
+    with oracle_on_cpu():
+        return restated_loop(small["oracle"], inp["latents"], OL.uniform_windows(small["F"], small["cf"], small["co"]), s,
+                             inp["kps_features"], inp["audio_embeddings"], steps, "ddim", s_a=s_a, **kw)
 
 
 def test_pipeline_three_rows_vs_restated_oracle_loop(small):

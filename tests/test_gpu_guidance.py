@@ -6,28 +6,12 @@ import torch
 
 import cases
 import guidance_restated as G
+from loop_restated import restated_loop
+from loop_worker import call_small, cosine, dev, oracle_on_cpu, rel_l2, scheduler, small  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 GUIDANCE, PHI = 3.5, 0.7
-
-
-def rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
-
-
-def cosine(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return (a @ b / (a.norm() * b.norm())).item()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    torch.cuda.set_device(0)
-    return "cuda"
 
 
 def predictions(nW, c, f, hw, mean, seed):
@@ -131,47 +115,21 @@ def test_kernel_argument_errors(dev):
 
 
 # ------------------------------------------------------------------------------------------------ (11) the pipeline
-@pytest.fixture(scope="module")
-def small(dev):
-    import dist_gpu_worker as W
-    from v_express_amd import synth
-    F_, cf, co, _ = cases.PIPELINE_CASES["reflected_F11_c4o2"]
-    cfg = cases.unet_cfg(cases.SMALL)
-    return dict(pipe=W.build_pipeline(dev), inp=synth.synthetic_inputs(cfg, F_, 8, 8), F=F_, cf=cf, co=co,
-                sd3=synth.unet3d_state_dict(cfg), sd2=synth.refnet_state_dict(cfg))
-
-
-def _call(S, steps, inp=None, guidance=cases.GUIDANCE, **kw):
-    from v_express_amd import DDIMScheduler
-    pipe, inp = S["pipe"], inp or S["inp"]
-    pipe.scheduler = DDIMScheduler(**G.KWARGS)
-    kw.setdefault("latents", inp["latents"])
-    return pipe(None, None, None, 64, 64, S["F"], steps, guidance, context_frames=S["cf"],
-                context_overlap=S["co"], reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD,
-                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
-                audio_embeddings=inp["audio_embeddings"], decode=False, **kw).cpu()
+def _call(S, steps, **kw):
+    return call_small(S, scheduler("ddim"), steps, **kw)
 
 
 def test_pipeline_with_both_features_vs_restated_oracle_loop(small):
-    from oracle import loop as OL, unet as OU
+    from oracle import loop as OL
     steps = 5
     got = _call(small, steps, guidance_rescale=PHI, guidance_end=0.6)
     assert small["pipe"].last_guidance["guided_steps"] == 3
     plain = _call(small, steps)
-    ocfg = cases.oracle_cfg(cases.SMALL)
     inp = small["inp"]
-    nthreads = torch.get_num_threads()
-    torch.set_num_threads(min(16, nthreads))
-    try:
-        with torch.no_grad():
-            banks = OU.reader_banks(OU.refnet_banks(small["sd2"], ocfg, inp["ref_latents"]))
-            ref = G.restated_loop(lambda x, t, e, k: OU.unet3d_forward(small["sd3"], ocfg, x, t, e, k, banks,
-                                                                       cases.W_REF, cases.W_AUD),
-                                  inp["latents"], OL.uniform_windows(small["F"], small["cf"], small["co"]),
-                                  cases.GUIDANCE, inp["kps_features"], inp["audio_embeddings"], steps, "ddim", phi=PHI,
-                                  end=0.6)
-    finally:
-        torch.set_num_threads(nthreads)
+    with oracle_on_cpu():
+        ref = restated_loop(small["oracle"], inp["latents"], OL.uniform_windows(small["F"], small["cf"], small["co"]),
+                            cases.GUIDANCE, inp["kps_features"], inp["audio_embeddings"], steps, "ddim", phi=PHI, end=0.6,
+                            unguided=("u", "c"))
     r, c = rel_l2(got, ref), cosine(got, ref)
     print(f"[DDIM, rescale {PHI}, guidance_end 0.6, SMALL, reflected_F11_c4o2, {steps} steps] relL2={r:.4g} "
           f"cosine={c:.6f} vs the restated loop; the clip without the controls: relL2={rel_l2(plain, ref):.4g}")

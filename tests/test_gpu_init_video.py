@@ -7,28 +7,13 @@ import torch
 
 import cases
 import init_video_restated as R
+from loop_restated import restated_loop
+from loop_worker import (build_small, call_pipeline, cosine, dev, inputs, oracle_on_cpu,  # noqa: F401
+                         oracle_unet, rel_l2, scheduler)
 
 pytestmark = pytest.mark.gpu
 
 ELEMS = [torch.bfloat16, torch.float16]
-
-
-def rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
-
-
-def cosine(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return (a @ b / (a.norm() * b.norm())).item()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    torch.cuda.set_device(0)
-    return "cuda"
 
 
 def table25():
@@ -206,27 +191,17 @@ def test_encode_video_chunks_and_oracle(dev):
 @pytest.fixture(scope="module")
 def small(dev):
     """The small pipeline with BOTH halves of the VAE (seeded synthetic encoder + decoder weights)."""
-    import dist_gpu_worker as W
     from v_express_amd import AutoencoderKL, synth
-    cfg = cases.unet_cfg(cases.SMALL)
+    S = build_small(dev)
     vcfg = synth.VaeConfig(**cases.SMALL_VAE)
-    pipe = W.build_pipeline(dev)
     vae = AutoencoderKL(vcfg).to(dev)
     vae.load_state_dict(dict(synth.vae_decoder_state_dict(vcfg), **synth.vae_encoder_state_dict(vcfg)))
-    pipe.vae = vae
-    return dict(pipe=pipe, cfg=cfg, sd3=synth.unet3d_state_dict(cfg), sd2=synth.refnet_state_dict(cfg))
+    S["pipe"].vae = vae
+    return S
 
 
 def _call(S, inp, F_, steps, cf, co, **kw):
-    from v_express_amd import DDIMScheduler
-    pipe = S["pipe"]
-    pipe.scheduler = DDIMScheduler(**R.KWARGS)
-    kw.setdefault("latents", inp["latents"])
-    kw.setdefault("decode", False)
-    return pipe(None, None, None, 64, 64, F_, steps, cases.GUIDANCE, context_frames=cf, context_overlap=co,
-                reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD,
-                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
-                audio_embeddings=inp["audio_embeddings"], **kw).cpu()
+    return call_pipeline(S["pipe"], scheduler("ddim"), inp, F_, steps, cf, co, **kw).cpu()
 
 
 def _mask(F_):
@@ -239,27 +214,18 @@ def _mask(F_):
 def test_pipeline_init_latents_and_mask_vs_restated_oracle_loop(small):
     """The CPU suite's first case on the device: F = 6, windows 4 / 2, 5 DDIM steps, strength 0.6, random init latents,
     frames 0-1 and the upper half of the others kept - the bounds of test_gpu_guidance.py's pipeline test."""
-    from oracle import loop as OL, unet as OU
-    from v_express_amd import synth
+    from oracle import loop as OL
     F_, cf, co, steps, strength = 6, 4, 2, 5, 0.6
-    inp = synth.synthetic_inputs(small["cfg"], F_, 8, 8)
+    inp = inputs(F_)
     init = 0.5 * torch.randn(1, 4, F_, 8, 8, generator=torch.Generator().manual_seed(5))
     mask = _mask(F_)
     got = _call(small, inp, F_, steps, cf, co, strength=strength, init_latents=init, mask=mask)
     assert small["pipe"].last_init == dict(begin_index=2, masked=True, blend_launches=4)
     plain = _call(small, inp, F_, steps, cf, co, strength=strength)
-    ocfg = cases.oracle_cfg(cases.SMALL)
-    nthreads = torch.get_num_threads()
-    torch.set_num_threads(min(16, nthreads))
-    try:
-        with torch.no_grad():
-            banks = OU.reader_banks(OU.refnet_banks(small["sd2"], ocfg, inp["ref_latents"]))
-            ref = R.restated_loop(lambda x, t, e, k: OU.unet3d_forward(small["sd3"], ocfg, x, t, e, k, banks,
-                                                                       cases.W_REF, cases.W_AUD),
-                                  init, inp["latents"], R.box_mean(mask[:, 0]), OL.uniform_windows(F_, cf, co),
-                                  cases.GUIDANCE, inp["kps_features"], inp["audio_embeddings"], steps, strength)
-    finally:
-        torch.set_num_threads(nthreads)
+    with oracle_on_cpu():
+        ref = restated_loop(oracle_unet(inp), inp["latents"], OL.uniform_windows(F_, cf, co), cases.GUIDANCE,
+                            inp["kps_features"], inp["audio_embeddings"], steps,
+                            known=(init, inp["latents"], R.box_mean(mask[:, 0]), strength))
     r, c = rel_l2(got, ref), cosine(got, ref)
     print(f"[DDIM, init_latents + mask, strength {strength}, SMALL, F = 6, {steps} steps] relL2={r:.4g} cosine={c:.6f} "
           f"vs the restated loop; the clip without init: relL2={rel_l2(plain, ref):.4g}")

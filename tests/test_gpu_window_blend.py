@@ -8,27 +8,11 @@ import torch
 import cases
 import dpm_restated as D
 import window_blend_restated as WB
+from loop_restated import restated_loop
+from loop_worker import (SEED, call_pipeline, cosine, dev, inputs, oracle_on_cpu, rel_l2,  # noqa: F401
+                         scheduler, small)
 
 pytestmark = pytest.mark.gpu
-SEED = (0x9E3779B9 << 32) | 0x7F4A7C15
-
-
-def rel_l2(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
-
-
-def cosine(a, b):
-    a, b = a.double().cpu().flatten(), b.double().cpu().flatten()
-    return (a @ b / (a.norm() * b.norm() + 1e-30)).item()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    torch.cuda.set_device(0)
-    return "cuda"
 
 
 def _windows(name, F_, f, o):
@@ -94,31 +78,9 @@ def test_blend_argument_errors_before_any_launch(dev):
 
 
 # ------------------------------------------------------------------------------------------------ the device loop
-@pytest.fixture(scope="module")
-def small(dev):
-    import dist_gpu_worker as W
-    from v_express_amd import synth
-    F_, cf, co, _ = cases.PIPELINE_CASES["reflected_F11_c4o2"]
-    cfg = cases.unet_cfg(cases.SMALL)
-    return dict(pipe=W.build_pipeline(dev), inp=synth.synthetic_inputs(cfg, F_, 8, 8), F=F_, cf=cf, co=co,
-                sd3=synth.unet3d_state_dict(cfg), sd2=synth.refnet_state_dict(cfg))
-
-
-def scheduler(kind):
-    from v_express_amd import DDIMScheduler, DPMSolverMultistepScheduler
-    return (DPMSolverMultistepScheduler if kind == "dpm" else DDIMScheduler)(**D.KWARGS)
-
-
 def _call(S, sched, steps, F_=None, **kw):
-    from v_express_amd import synth
-    pipe = S["pipe"]
     F_ = F_ or S["F"]
-    inp = S["inp"] if F_ == S["F"] else synth.synthetic_inputs(cases.unet_cfg(cases.SMALL), F_, 8, 8)
-    pipe.scheduler = sched
-    return pipe(None, None, None, 64, 64, F_, steps, cases.GUIDANCE, context_frames=S["cf"], context_overlap=S["co"],
-                reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD,
-                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
-                audio_embeddings=inp["audio_embeddings"], latents=inp["latents"], decode=False, **kw).cpu()
+    return call_pipeline(S["pipe"], sched, inputs(F_), F_, steps, S["cf"], S["co"], **kw).cpu()
 
 
 @pytest.mark.parametrize("kind", ["ddim", "dpm"])
@@ -126,7 +88,6 @@ def test_pipeline_uniform_fit_linear_vs_restated_oracle_loop(small, kind):
     """SMALL, F 11 in even-fit windows of 4 with overlap 2, 6 steps: rel-L2 <= 5e-2 and cosine >= 0.998 against the
     float64-weighted restated loop (tests/test_gpu_dpm_solver.py's bound for this pipeline); the mean route's pair from
     the same run is printed next to it."""
-    import audio_guidance_restated as AG
     steps = 6
     F_, cf, co = small["F"], small["cf"], small["co"]
     assert (F_, cf, co) == (11, 4, 2)
@@ -137,17 +98,10 @@ def test_pipeline_uniform_fit_linear_vs_restated_oracle_loop(small, kind):
                                               blend_launches=steps)
     mean = _call(small, scheduler(kind), steps, **fit)
     inp = small["inp"]
-    unet = AG.oracle_rows_unet(small["sd3"], small["sd2"], cases.oracle_cfg(cases.SMALL), inp["ref_latents"], cases.W_REF,
-                               cases.W_AUD)
-    nthreads = torch.get_num_threads()
-    torch.set_num_threads(min(16, nthreads))
-    try:
-        with torch.no_grad():
-            ref, ref_mean = (WB.restated_loop(unet, inp["latents"], windows, raw, cases.GUIDANCE, inp["kps_features"],
-                                              inp["audio_embeddings"], steps, kind)
-                             for raw in (WB.raw_weights(windows, "linear"), None))
-    finally:
-        torch.set_num_threads(nthreads)
+    with oracle_on_cpu():
+        ref, ref_mean = (restated_loop(small["oracle"], inp["latents"], windows, cases.GUIDANCE, inp["kps_features"],
+                                       inp["audio_embeddings"], steps, kind, raw=raw)
+                         for raw in (WB.raw_weights(windows, "linear"), None))
     r, c = rel_l2(got, ref), cosine(got, ref)
     rm, cm = rel_l2(mean, ref_mean), cosine(mean, ref_mean)
     print(f"[{kind}, SMALL, uniform_fit F11 c4 o2, {steps} steps] linear: relL2={r:.4g} cosine={c:.6f}; mean: "

@@ -2,75 +2,17 @@
 `guidance_end`) of VExpressPipeline under emulated kernels (tests/fake_ops.py + guidance_restated.guidance_rescale)
 against float64 restatements, the step rule against a table, the unguided steps against the no-CFG route bit for bit,
 every sampler with both features on, the argument errors, and two gloo ranks against one process."""
-import os
-import socket
-
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import ancestral_restated as A
 import cases
 import dpm_restated as D
 import guidance_restated as G
+from loop_restated import restated_loop
+from loop_worker import (SEED, call_pipeline as _call, emulated, inputs as _inputs,  # noqa: F401
+                         oracle_unet as _oracle_unet, rel_l2, scheduler, small_pipe, spawn_gloo)
 
-SEED = (0x9E3779B9 << 32) | 0x7F4A7C15
 PHI = 0.7
-
-
-def rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
-
-
-@pytest.fixture()
-def emulated(monkeypatch):
-    import fake_ops
-    from v_express_amd import ops, prologue, unet_3d, vae
-    fake_ops.install(monkeypatch, ops)
-    monkeypatch.setattr(ops, "overlap_ancestral_step", A.overlap_ancestral_step)
-    monkeypatch.setattr(ops, "overlap_multistep_step", D.overlap_multistep_step)
-    monkeypatch.setattr(ops, "guidance_rescale", G.guidance_rescale)
-    monkeypatch.setattr(unet_3d._UNetBase, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(vae.AutoencoderKLDecoder, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(prologue._Module, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(ops, "_PADDED", {})
-    return ops
-
-
-@pytest.fixture(scope="module")
-def small_pipe():
-    import dist_gpu_worker as W
-    return W.build_pipeline("cpu")
-
-
-def scheduler(kind):
-    from v_express_amd import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
-    return {"ddim": DDIMScheduler, "ddim-eta": DDIMScheduler, "dpm": DPMSolverMultistepScheduler,
-            "euler-a": EulerAncestralDiscreteScheduler}[kind](**G.KWARGS)
-
-
-def _call(pipe, sched, inp, F_, steps, cf, co, guidance=cases.GUIDANCE, **kw):
-    pipe.scheduler = sched
-    kw.setdefault("latents", inp["latents"])
-    return pipe(None, None, None, 64, 64, F_, steps, guidance, context_frames=cf, context_overlap=co,
-                reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD,
-                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
-                audio_embeddings=inp["audio_embeddings"], decode=False, **kw)
-
-
-def _inputs(F_):
-    from v_express_amd import synth
-    return synth.synthetic_inputs(cases.unet_cfg(cases.SMALL), F_, 8, 8)
-
-
-def _oracle_unet(inp):
-    from oracle import unet as OU
-    from v_express_amd import synth
-    cfg, ocfg = cases.unet_cfg(cases.SMALL), cases.oracle_cfg(cases.SMALL)
-    sd3, sd2 = synth.unet3d_state_dict(cfg), synth.refnet_state_dict(cfg)
-    banks = OU.reader_banks(OU.refnet_banks(sd2, ocfg, inp["ref_latents"]))
-    return lambda x, t, e, k: OU.unet3d_forward(sd3, ocfg, x, t, e, k, banks, cases.W_REF, cases.W_AUD)
 
 
 # ------------------------------------------------------------------------------------------------ (1) the rescale
@@ -106,8 +48,8 @@ def test_guidance_rescale_changes_the_clip_and_matches_the_restatement(emulated,
         print(f"[guidance_rescale stand-in] max |err| {err:.3g}, float32 torch.std baseline {base:.3g}")
         assert err <= 4 * base
     with torch.no_grad():
-        ref = G.restated_loop(_oracle_unet(inp), inp["latents"], windows, cases.GUIDANCE, inp["kps_features"],
-                              inp["audio_embeddings"], steps, "ddim", phi=PHI)
+        ref = restated_loop(_oracle_unet(inp), inp["latents"], windows, cases.GUIDANCE, inp["kps_features"],
+                            inp["audio_embeddings"], steps, "ddim", phi=PHI)
     r = rel_l2(got, ref)
     print(f"[__call__ guidance_rescale={PHI}, emulated kernels, {steps} steps] relL2 vs restated loop {r:.4g}, "
           f"vs phi = 0 {rel_l2(plain, ref):.4g}")
@@ -220,9 +162,9 @@ def test_every_sampler_with_both_features_vs_restated_loop(emulated, small_pipe,
                 **kw)
     assert small_pipe.last_guidance["guided_steps"] == 3 and small_pipe.last_guidance["steps"] == 5
     with torch.no_grad():
-        ref = G.restated_loop(_oracle_unet(inp), inp["latents"], OL.uniform_windows(F_, cf, co), cases.GUIDANCE,
-                              inp["kps_features"], inp["audio_embeddings"], steps, kind, phi=PHI, end=0.6, seed=SEED,
-                              eta=eta)
+        ref = restated_loop(_oracle_unet(inp), inp["latents"], OL.uniform_windows(F_, cf, co), cases.GUIDANCE,
+                            inp["kps_features"], inp["audio_embeddings"], steps, kind, phi=PHI, end=0.6,
+                            unguided=("u", "c"), seed=SEED, eta=eta)
     r = rel_l2(got, ref)
     print(f"[__call__ {kind}, rescale {PHI}, guidance_end 0.6, reflected_F11_c4o2, {steps} steps] relL2 vs restated "
           f"loop {r:.4g}")
@@ -264,13 +206,6 @@ def test_ops_wrapper_checks_its_arguments():
 
 
 # ------------------------------------------------------------------------------------------------ (7) two ranks
-def _worker(rank, world, port, q, frame_shards, latent):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    import guidance_worker
-    lat, sched, guid = guidance_worker.main(frame_shards, latent)
-    q.put((rank, lat.numpy().copy(), sched, guid))             # by value (see test_host_emulated._worker)
-
-
 @pytest.mark.parametrize("frame_shards,latent", [(None, 8), (2, 16)])
 def test_two_gloo_ranks_are_bit_identical_to_one_process(emulated, frame_shards, latent):
     """F = 14, windows 8 / 2, guidance_rescale = 0.7, guidance_end = 0.6 (3 guided + 2 unguided DDIM steps): the partials
@@ -278,20 +213,8 @@ def test_two_gloo_ranks_are_bit_identical_to_one_process(emulated, frame_shards,
     unit frame-sharded two ways) give the bits of one process, on both ranks."""
     import guidance_worker
     ref, _, _ = guidance_worker.run(None, latent)
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q, frame_shards, latent)) for r in range(2)]
-    for p in procs:
-        p.start()
-    results = [q.get(timeout=900) for _ in procs]
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    for rank, lat, sched, guid in results:
-        lat = torch.from_numpy(lat)
+    results = spawn_gloo(guidance_worker.main, 2, frame_shards, latent, timeout=900)
+    for rank, (lat, sched, guid) in enumerate(results):
         assert torch.isfinite(lat).all() and torch.equal(lat, ref), (rank, rel_l2(lat, ref))
         assert sched["frame_shards"] == (frame_shards or 1) and sched["units"] == 4 and sched["world"] == 2
         assert guid["unguided_schedule"]["units"] == 2 and guid["guided_steps"] == 3

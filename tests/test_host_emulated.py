@@ -9,10 +9,10 @@ import socket
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 import cases
 import dist_gpu_worker as W
+from loop_worker import emulated, spawn_gloo  # noqa: F401
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -20,18 +20,6 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 def rel_l2(a, b):
     a, b = a.float(), b.float()
     return ((a - b).norm() / (b.norm() + 1e-12)).item()
-
-
-@pytest.fixture()
-def emulated(monkeypatch):
-    import fake_ops
-    from v_express_amd import ops, prologue, unet_3d, vae
-    fake_ops.install(monkeypatch, ops)
-    monkeypatch.setattr(unet_3d._UNetBase, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(vae.AutoencoderKLDecoder, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(prologue._Module, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(ops, "_PADDED", {})
-    return ops
 
 
 @pytest.mark.parametrize("name", ["small_f4_8x8", "small_f8_16x8", "full_f4_8x8"])      # full = the SD-1.5 widths
@@ -200,16 +188,10 @@ def test_prologue_models_host_composition_vs_reference_golden(emulated):
     assert rel_l2(v.encode(inp["ref_image"]).latent_dist.mean, g["vae_mean"]) <= 2e-2
 
 
-def _worker(rank, world, port, F, cf, co, S, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    import torch.distributed as dist
+def _worker(rank, F, cf, co, S):
     torch.set_num_threads(2)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     W.emulate_kernels()
-    lat = W.run(F, cf, co, 2, S, device="cpu")
-    q.put((rank, lat.float().numpy().copy()))      # by value: a tensor's file descriptor must be fetched while this process lives
-    dist.barrier()
-    dist.destroy_process_group()
+    return W.run(F, cf, co, 2, S, device="cpu").float()
 
 
 @pytest.mark.parametrize("world,S,F,cf,co", [(2, 2, 8, 8, 2), (4, 0, 8, 8, 2), (2, 1, 14, 8, 2), (4, 1, 32, 8, 2)])
@@ -220,19 +202,7 @@ def test_sharded_loop_with_the_real_host_code_matches_single_process(emulated, w
     inside, bf16 at the boundaries) give a row the same result whatever else shares the call, so sharding is pure data
     movement and the clip must come out BIT-identical, on every rank."""
     ref = W.run(F, cf, co, 2, 0, device="cpu")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, F, cf, co, S, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = [(r, torch.from_numpy(a)) for r, a in (q.get(timeout=600) for _ in procs)]
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    for rank, lat in results:
+    for rank, lat in enumerate(spawn_gloo(_worker, world, F, cf, co, S, timeout=600)):
         assert torch.isfinite(lat).all() and torch.equal(lat, ref), (rank, rel_l2(lat, ref))
 
 
@@ -248,19 +218,7 @@ def test_sharded_loop_with_the_round4_paths_forced_on(emulated, monkeypatch, wor
     monkeypatch.setenv("VX_TEST_FORCE_ROUND4", "1")
     ref = W.run(F, cf, co, 2, 0, device="cpu")
     assert not torch.equal(ref, default) and rel_l2(ref, default) <= 3e-2
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, F, cf, co, S, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    results = [(r, torch.from_numpy(a)) for r, a in (q.get(timeout=600) for _ in procs)]
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    for rank, lat in results:
+    for rank, lat in enumerate(spawn_gloo(_worker, world, F, cf, co, S, timeout=600)):
         assert torch.isfinite(lat).all() and torch.equal(lat, ref), (rank, rel_l2(lat, ref))
 
 
@@ -377,12 +335,9 @@ def test_merging_windows_into_one_unet_call_changes_nothing(emulated):
     assert torch.equal(got, ref)
 
 
-def _call_worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    import torch.distributed as dist
+def _call_worker(rank):
     torch.set_num_threads(2)
     torch.manual_seed(1000 + rank)                 # every rank's default generator differs, as in a real launch
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     W.emulate_kernels()
     from v_express_amd import synth
     pipe = W.build_pipeline("cpu")
@@ -393,26 +348,13 @@ def _call_worker(rank, world, port, q):
                reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD, generator=None,
                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
                audio_embeddings=inp["audio_embeddings"], decode=False)
-    q.put((rank, lat.float().numpy().copy()))      # by value (see _worker)
-    dist.barrier()
-    dist.destroy_process_group()
+    return lat.float()
 
 
 def test_call_without_generator_gives_every_rank_the_same_clip():
     """with generator=None every rank draws its own noise; `__call__` must broadcast rank 0's draw, or the
     per-step all-gather mixes predictions of different clips.  Two gloo ranks, different default-generator seeds."""
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_call_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    results = {r: torch.from_numpy(a) for r, a in (q.get(timeout=600) for _ in procs)}
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    results = spawn_gloo(_call_worker, 2, timeout=600)
     assert torch.isfinite(results[0]).all() and torch.equal(results[0], results[1])
 
 

@@ -209,11 +209,11 @@ def test_wav2vec2_host_composition_with_emulated_kernels(tag, monkeypatch):
     HIP wrappers (fp32 math, bf16 rounding at each kernel boundary) and compared with the fp32 oracle.  The GPU suite
     runs the same code on the real kernels (tests/test_gpu_prologue.py)."""
     import cases
-    import fake_ops
+    import loop_worker
     from oracle import wav2vec2 as OW
     from v_express_amd import ops
     from v_express_amd.wav2vec2 import Wav2Vec2Model, WaveformProcessor
-    fake_ops.install(monkeypatch, ops)
+    loop_worker.emulate_kernels(monkeypatch)
     monkeypatch.setattr(Wav2Vec2Model, "_need_gpu", lambda self: None)
     kw, samples = cases.W2V_CASES[tag]
     cfg = synth.Wav2Vec2Config(**kw)
@@ -458,12 +458,12 @@ def test_audio_encoder_directory_loader(tmp_path, monkeypatch):
     one emulated forward against the oracle."""
     import json
     import cases
-    import fake_ops
+    import loop_worker
     from safetensors.torch import save_file
     from oracle import wav2vec2 as OW
     from v_express_amd import checkpoints, ops
     from v_express_amd.wav2vec2 import Wav2Vec2Model
-    fake_ops.install(monkeypatch, ops)
+    loop_worker.emulate_kernels(monkeypatch)
     monkeypatch.setattr(Wav2Vec2Model, "_need_gpu", lambda self: None)
     kw, samples = cases.W2V_CASES["small"]
     cfg = synth.Wav2Vec2Config(**kw)

@@ -3,77 +3,26 @@
 vae_postprocess_composite) against float64 restatements of diffusers' img2img start and inpaint loop, for every sampler;
 the exact identities of the blend, the untouched default path, the schedulers' noise_coefficients / add_noise, the
 argument errors, and two gloo ranks against one process."""
-import os
-import socket
-
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import ancestral_restated as A
 import cases
 import dpm_restated as D
 import init_video_restated as R
+import loop_worker
+from loop_restated import restated_loop
+from loop_worker import (SEED, call_pipeline as _call, inputs as _inputs, oracle_unet as _oracle_unet,  # noqa: F401
+                         rel_l2, sampler_kw, scheduler, small_pipe, spawn_gloo)
 
-SEED = (0x9E3779B9 << 32) | 0x7F4A7C15
 KINDS = ["ddim", "ddim-eta", "dpm", "euler-a"]
-
-
-def rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
 
 
 @pytest.fixture()
 def emulated(monkeypatch):
-    import fake_ops
-    from v_express_amd import ops, prologue, unet_3d, vae
-    fake_ops.install(monkeypatch, ops)
-    monkeypatch.setattr(ops, "overlap_ancestral_step", A.overlap_ancestral_step)
-    monkeypatch.setattr(ops, "overlap_multistep_step", D.overlap_multistep_step)
-    monkeypatch.setattr(ops, "known_blend", R.known_blend)
+    """The shared emulation plus the stand-in of the one kernel of this feature that is no loop op."""
+    ops = loop_worker.emulate_kernels(monkeypatch)
     monkeypatch.setattr(ops, "vae_postprocess_composite", R.vae_postprocess_composite)
-    monkeypatch.setattr(unet_3d._UNetBase, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(vae.AutoencoderKLDecoder, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(prologue._Module, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(ops, "_PADDED", {})
     return ops
-
-
-@pytest.fixture(scope="module")
-def small_pipe():
-    import dist_gpu_worker as W
-    return W.build_pipeline("cpu")
-
-
-def scheduler(kind):
-    from v_express_amd import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
-    return {"ddim": DDIMScheduler, "ddim-eta": DDIMScheduler, "dpm": DPMSolverMultistepScheduler,
-            "euler-a": EulerAncestralDiscreteScheduler}[kind](**R.KWARGS)
-
-
-def _call(pipe, sched, inp, F_, steps, cf, co, guidance=cases.GUIDANCE, **kw):
-    pipe.scheduler = sched
-    kw.setdefault("latents", inp["latents"])
-    kw.setdefault("decode", False)
-    return pipe(None, None, None, 64, 64, F_, steps, guidance, context_frames=cf, context_overlap=co,
-                reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD,
-                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
-                audio_embeddings=inp["audio_embeddings"], **kw)
-
-
-def _inputs(F_):
-    from v_express_amd import synth
-    return synth.synthetic_inputs(cases.unet_cfg(cases.SMALL), F_, 8, 8)
-
-
-def _oracle_unet(inp):
-    from oracle import unet as OU
-    from v_express_amd import synth
-    cfg, ocfg = cases.unet_cfg(cases.SMALL), cases.oracle_cfg(cases.SMALL)
-    sd3, sd2 = synth.unet3d_state_dict(cfg), synth.refnet_state_dict(cfg)
-    banks = OU.reader_banks(OU.refnet_banks(sd2, ocfg, inp["ref_latents"]))
-    return lambda x, t, e, k: OU.unet3d_forward(sd3, ocfg, x, t, e, k, banks, cases.W_REF, cases.W_AUD)
 
 
 def _init(F_, seed=5):
@@ -86,13 +35,6 @@ def _mask(F_, edge=32):
     m[:2] = 0.0
     m[:, :, :edge] = 0.0
     return m
-
-
-def _sampler_kw(kind):
-    kw = dict(eta=0.5 if kind == "ddim-eta" else 0.0)
-    if kind in ("ddim-eta", "euler-a"):
-        kw["noise_seed"] = SEED
-    return kw
 
 
 # ------------------------------------------------------------------------------------------------ (1) the feature
@@ -112,8 +54,8 @@ def test_init_latents_and_mask_change_the_clip_and_match_the_restatement(emulate
     m = R.box_mean(mask[:, 0])
     assert set(m.unique().tolist()) == {0.0, 1.0} and m[:2].sum() == 0 and m[2:, :32].sum() == 0 and m[2:, 32:].all()
     with torch.no_grad():
-        ref = R.restated_loop(_oracle_unet(inp), init, inp["latents"], m, OL.uniform_windows(F_, cf, co),
-                              cases.GUIDANCE, inp["kps_features"], inp["audio_embeddings"], steps, strength)
+        ref = restated_loop(_oracle_unet(inp), inp["latents"], OL.uniform_windows(F_, cf, co), cases.GUIDANCE,
+                            inp["kps_features"], inp["audio_embeddings"], steps, known=(init, inp["latents"], m, strength))
     r, r_plain = rel_l2(got, ref), rel_l2(plain, ref)
     print(f"[__call__ init_latents + mask, strength {strength}, emulated kernels, {steps} DDIM steps] relL2 vs restated "
           f"loop {r:.4g}; the clip without init: {r_plain:.4g}")
@@ -151,12 +93,12 @@ def test_every_sampler_vs_restated_loop_and_kept_cells_after_every_step(emulated
         seen.append(i)
         assert (err[keep] <= bound[keep]).all(), (kind, i, (err[keep] - bound[keep]).max().item())
     got = _call(small_pipe, sched, inp, F_, steps, cf, co, strength=strength, init_latents=init, mask=mask,
-                callback=check, **_sampler_kw(kind))
+                callback=check, **sampler_kw(kind, 0.5))
     assert seen == [0, 1, 2] and small_pipe.last_init == dict(begin_index=b, masked=True, blend_launches=4)
     with torch.no_grad():
-        ref = R.restated_loop(_oracle_unet(inp), init, noise, m, OL.uniform_windows(F_, cf, co), cases.GUIDANCE,
-                              inp["kps_features"], inp["audio_embeddings"], steps, strength, kind, seed=SEED,
-                              eta=0.5 if kind == "ddim-eta" else 0.0)
+        ref = restated_loop(_oracle_unet(inp), noise, OL.uniform_windows(F_, cf, co), cases.GUIDANCE,
+                            inp["kps_features"], inp["audio_embeddings"], steps, kind, seed=SEED,
+                            eta=0.5 if kind == "ddim-eta" else 0.0, known=(init, noise, m, strength))
     r = rel_l2(got, ref)
     print(f"[__call__ {kind}, init_latents + soft mask, strength {strength}, reflected_F11_c4o2, {steps} steps] relL2 vs "
           f"restated loop {r:.4g}")
@@ -192,7 +134,7 @@ def test_mask_of_zeros_returns_the_init_latents_exactly(emulated, small_pipe, ki
     F_, cf, co, steps = 6, 4, 2, 3
     inp, init = _inputs(F_), _init(F_, seed=9)
     got = _call(small_pipe, scheduler(kind), inp, F_, steps, cf, co, strength=0.7, init_latents=init,
-                mask=torch.zeros(F_, 1, 64, 64, dtype=torch.bool), **_sampler_kw(kind))
+                mask=torch.zeros(F_, 1, 64, 64, dtype=torch.bool), **sampler_kw(kind, 0.5))
     assert small_pipe.last_init == dict(begin_index=1, masked=True, blend_launches=3)
     assert torch.equal(got, init)
 
@@ -413,13 +355,6 @@ def test_mask_forms_and_the_latent_box_mean():
 
 
 # ------------------------------------------------------------------------------------------------ (7) two ranks
-def _worker(rank, world, port, q, frame_shards, latent):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    import init_video_worker
-    lat, sched, last = init_video_worker.main(frame_shards, latent)
-    q.put((rank, lat.numpy().copy(), sched, last))               # by value (see test_host_emulated._worker)
-
-
 @pytest.mark.parametrize("frame_shards,latent", [(None, 8), (2, 16)])
 def test_two_gloo_ranks_are_bit_identical_to_one_process(emulated, frame_shards, latent):
     """F = 14, windows 8 / 2, init latents + mask, strength 0.6 (3 of 5 DDIM steps), no generator: each rank draws its
@@ -430,20 +365,8 @@ def test_two_gloo_ranks_are_bit_identical_to_one_process(emulated, frame_shards,
     if latent == 8:
         other, _, _ = init_video_worker.run(None, latent, rank=1)
         assert not torch.equal(ref, other)                       # rank 1's own draw would give another clip
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q, frame_shards, latent)) for r in range(2)]
-    for p in procs:
-        p.start()
-    results = [q.get(timeout=900) for _ in procs]
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    for rank, lat, sched, last in results:
-        lat = torch.from_numpy(lat)
+    results = spawn_gloo(init_video_worker.main, 2, frame_shards, latent, timeout=900)
+    for rank, (lat, sched, last) in enumerate(results):
         assert torch.isfinite(lat).all() and torch.equal(lat, ref), (rank, rel_l2(lat, ref))
         assert sched["frame_shards"] == (frame_shards or 1) and sched["units"] == 4 and sched["world"] == 2
         assert last == dict(begin_index=2, masked=True, blend_launches=4)

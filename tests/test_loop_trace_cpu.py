@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import loop_trace as T  # noqa: E402
+from loop_worker import small_pipe  # noqa: E402,F401
 
 REL = 1e-6
 
@@ -23,12 +24,6 @@ REL = 1e-6
 def golden():
     with open(os.path.join(HERE, "golden", "denoise_launch_trace.json")) as fh:
         return json.load(fh)
-
-
-@pytest.fixture(scope="module")
-def small_pipe():
-    import dist_gpu_worker as W
-    return W.build_pipeline("cpu")
 
 
 def differences(got, want, where, out):

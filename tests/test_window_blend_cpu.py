@@ -5,36 +5,23 @@ restatements over the oracle UNet: the schedule's properties over a grid, the we
 kernel's bound, every sampler, the defaults and the ones profile bit for bit, the composition with the guidance controls
 and init-video sampling, two gloo ranks against one process, the symbol and the C entry point's argument checks."""
 import ctypes
-import math
-import os
 import random
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import ancestral_restated as A
-import audio_guidance_restated as AG
 import cases
-import dpm_restated as D
-import guidance_restated as G
 import init_video_restated as R
 import window_blend_restated as WB
+from loop_restated import restated_loop
+from loop_worker import (SEED, UPDATES, call_pipeline as _call, emulated, inputs as _inputs,  # noqa: F401
+                         oracle_unet as _oracle_unet, rel_l2, sampler_kw as _sampler_kw, scheduler, small_pipe,
+                         spawn_gloo, trace_ops as _trace)
 
-SEED = (0x9E3779B9 << 32) | 0x7F4A7C15
 S = cases.GUIDANCE
 BOUND = 5e-2        # the relative-L2 bound tests/test_audio_guidance_cpu.py applies to the same loop at these geometries
 F11 = (11, 4, 2)    # F, context frames, overlap: even-fit starts 0, 1, 3, 5, 7 - frame 3 lies in three windows
-UPDATES = ("overlap_ddim_step", "overlap_multistep_step", "overlap_ancestral_step")
-LOOP_OPS = ("gather_latents", "pack_rows", "combine_units", "guidance_rescale", "combine_units3", "guidance_rescale3",
-            "overlap_blend", "known_blend") + UPDATES
-
-
-def rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
 
 
 def sched_windows(name, F_, f, o):
@@ -228,81 +215,6 @@ def test_restated_kernel_within_its_bound_of_float64(mean):
 
 
 # ------------------------------------------------------------------------------------------------ the emulated pipeline
-@pytest.fixture()
-def emulated(monkeypatch):
-    import fake_ops
-    from v_express_amd import ops, prologue, unet_3d, vae
-    fake_ops.install(monkeypatch, ops)
-    monkeypatch.setattr(ops, "overlap_ancestral_step", A.overlap_ancestral_step)
-    monkeypatch.setattr(ops, "overlap_multistep_step", D.overlap_multistep_step)
-    monkeypatch.setattr(ops, "guidance_rescale", G.guidance_rescale)
-    monkeypatch.setattr(ops, "known_blend", R.known_blend)
-    monkeypatch.setattr(ops, "combine_units3", AG.combine_units3)
-    monkeypatch.setattr(ops, "guidance_rescale3", AG.guidance_rescale3)
-    monkeypatch.setattr(ops, "overlap_blend", WB.overlap_blend)
-    monkeypatch.setattr(unet_3d._UNetBase, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(vae.AutoencoderKLDecoder, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(prologue._Module, "_need_gpu", lambda self: None)
-    monkeypatch.setattr(ops, "_PADDED", {})
-    return ops
-
-
-@pytest.fixture(scope="module")
-def small_pipe():
-    import dist_gpu_worker as W
-    return W.build_pipeline("cpu")
-
-
-def scheduler(kind):
-    from v_express_amd import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
-    return {"ddim": DDIMScheduler, "ddim-eta": DDIMScheduler, "dpm": DPMSolverMultistepScheduler,
-            "euler-a": EulerAncestralDiscreteScheduler}[kind](**G.KWARGS)
-
-
-def _call(pipe, sched, inp, F_, steps, cf, co, guidance=S, **kw):
-    pipe.scheduler = sched
-    kw.setdefault("latents", inp["latents"])
-    return pipe(None, None, None, 64, 64, F_, steps, guidance, context_frames=cf, context_overlap=co,
-                reference_attention_weight=cases.W_REF, audio_attention_weight=cases.W_AUD,
-                reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
-                audio_embeddings=inp["audio_embeddings"], decode=False, **kw)
-
-
-_INPUTS = {}
-
-
-def _inputs(F_):
-    from v_express_amd import synth
-    if F_ not in _INPUTS:
-        _INPUTS[F_] = synth.synthetic_inputs(cases.unet_cfg(cases.SMALL), F_, 8, 8)
-    return _INPUTS[F_]
-
-
-def _oracle_unet(inp):
-    from v_express_amd import synth
-    cfg, ocfg = cases.unet_cfg(cases.SMALL), cases.oracle_cfg(cases.SMALL)
-    return AG.oracle_rows_unet(synth.unet3d_state_dict(cfg), synth.refnet_state_dict(cfg), ocfg, inp["ref_latents"],
-                               cases.W_REF, cases.W_AUD)
-
-
-def _trace(monkeypatch, ops, names=LOOP_OPS):
-    """Records the names of the loop's ops as they are called."""
-    trace = []
-    for name in names:
-        def wrap(*a, _fn=getattr(ops, name), _name=name, **k):
-            trace.append(_name)
-            return _fn(*a, **k)
-        monkeypatch.setattr(ops, name, wrap)
-    return trace
-
-
-def _sampler_kw(kind, eta=1.0):
-    kw = dict(eta=eta if kind == "ddim-eta" else 0.0)
-    if kind in ("ddim-eta", "euler-a"):
-        kw["noise_seed"] = SEED
-    return kw
-
-
 @pytest.mark.parametrize("kind", ["ddim", "dpm", "ddim-eta", "euler-a"])
 def test_weighted_clips_match_the_restated_loop(emulated, small_pipe, monkeypatch, kind):
     """F 11 in even-fit windows of 4 with overlap 2 (starts 0, 1, 3, 5, 7), 3 steps of DDIM, DPM++ 2M, DDIM eta = 1 and
@@ -330,8 +242,8 @@ def test_weighted_clips_match_the_restated_loop(emulated, small_pipe, monkeypatc
         assert tail == ["combine_units", "overlap_blend", update] * steps
         assert torch.isfinite(got).all() and rel_l2(got, mean) > 1e-3
         with torch.no_grad():
-            ref = WB.restated_loop(unet, inp["latents"], windows, WB.raw_weights(windows, blend), S, inp["kps_features"],
-                                   inp["audio_embeddings"], steps, kind, seed=SEED, eta=skw["eta"])
+            ref = restated_loop(unet, inp["latents"], windows, S, inp["kps_features"], inp["audio_embeddings"], steps,
+                                kind, seed=SEED, eta=skw["eta"], raw=WB.raw_weights(windows, blend))
         r = rel_l2(got, ref)
         print(f"[__call__ {kind}, uniform_fit F11 c4 o2, overlap_blend={blend}, {steps} steps, emulated kernels] relL2 vs "
               f"the restated weighted loop {r:.4g}; the mean clip {rel_l2(mean, ref):.4g}")
@@ -443,8 +355,8 @@ def test_linear_composes_with_the_other_controls(emulated, small_pipe, monkeypat
         assert small_pipe.last_init == dict(begin_index=2, masked=True, blend_launches=4)
         assert torch.equal(got[:, :, :2], init[:, :, :2]) and torch.equal(got[..., :4, :], init[..., :4, :])
     with torch.no_grad():
-        ref = WB.restated_loop(_oracle_unet(inp), inp["latents"], windows, raw, S, inp["kps_features"],
-                               inp["audio_embeddings"], steps, "ddim", **rkw)
+        ref = restated_loop(_oracle_unet(inp), inp["latents"], windows, S, inp["kps_features"], inp["audio_embeddings"],
+                            steps, "ddim", raw=raw, **rkw)
     r = rel_l2(got, ref)
     print(f"[__call__ ddim, uniform_fit F7 c4 o2, linear + {case}, {steps} steps, emulated kernels] relL2 vs the restated "
           f"loop {r:.4g}")
@@ -537,13 +449,6 @@ def test_c_entry_point_validates_before_any_launch():
 
 
 # ------------------------------------------------------------------------------------------------ two ranks
-def _worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    import window_blend_worker
-    lat, sched, over = window_blend_worker.main()
-    q.put((rank, lat.numpy().copy(), sched, over))             # by value (see test_host_emulated._worker)
-
-
 def test_two_gloo_ranks_are_bit_identical_to_one_process(emulated):
     """Three windows x two CFG halves on two gloo ranks with the "linear" blend (the blend, like the update, runs
     redundantly on every rank): the bits of one process, on both ranks."""
@@ -552,20 +457,8 @@ def test_two_gloo_ranks_are_bit_identical_to_one_process(emulated):
     assert over == dict(schedule=None, blend="linear", windows=3, max_terms=3, blend_launches=window_blend_worker.STEPS)
     mean, _, _ = window_blend_worker.run(blend="mean")
     assert not torch.equal(ref, mean)
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    results = [q.get(timeout=900) for _ in procs]
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    for rank, lat, sched, got_over in results:
-        lat = torch.from_numpy(lat)
+    results = spawn_gloo(window_blend_worker.main, 2, timeout=900)
+    for rank, (lat, sched, got_over) in enumerate(results):
         assert torch.isfinite(lat).all() and torch.equal(lat, ref), (rank, rel_l2(lat, ref))
         assert sched == dict(kind="whole units", frame_shards=1, mixed_shards=1, units=6, world=2)
         assert got_over == over

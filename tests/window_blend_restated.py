@@ -1,18 +1,12 @@
 """Restatements of the weighted window blend (TEST INFRASTRUCTURE) for tests/test_window_blend_cpu.py and
 tests/test_gpu_window_blend.py: the even-fit window starts and the raw weights ("linear", "pyramid") written out from
-their definitions, the per-frame plan, `ops.overlap_blend` in float32 torch arithmetic (the kernel's bits: one rounding per
-product and per sum, the first valid term initialises) and in float64 with its bound, and the loop of
-pipelines/v_express_pipeline.py:526-583 in float64 over the oracle UNet with per-frame normalised weights in place of the
-1 / count of :552-572 - every sampler, the rescale, a guidance interval, a separate audio scale and init-video sampling."""
+their definitions, the per-frame plan with its normalised weights, and `ops.overlap_blend` in float32 torch arithmetic
+(the kernel's bits: one rounding per product and per sum, the first valid term initialises) and in float64 with its bound.
+The loop that uses them is tests/loop_restated.py."""
 import math
 
 import torch
 
-import ancestral_restated as A
-import audio_guidance_restated as AG
-import dpm_restated as D
-import guidance_restated as G
-import init_video_restated as R
 
 U = 2.0 ** -24                    # unit roundoff of float32
 
@@ -136,79 +130,3 @@ def overlap_blend64(preds, terms, weights):
         term = torch.where((slot >= 0)[:, None, None], term, torch.zeros_like(term))
         v, mag = v + term, mag + term.abs()
     return v.permute(1, 0, 2), (2 * T * U * mag).permute(1, 0, 2)
-
-
-# ------------------------------------------------------------------------------------------------ the loop
-def restated_loop(unet_fn, latents, windows, raw, s, kps_feature, audio_embeddings, n, sampler="ddim", s_a=None, phi=0.0,
-                  start=0.0, end=1.0, seed=None, eta=0.0, known=None):
-    """audio_guidance_restated.restated_loop (`unet_fn` of AG.oracle_rows_unet; conditioning in the CFG layout) with every
-    frame's prediction the weighted sum of the windows that hold it - float64 weights raw / sum(raw of the frame), raw
-    [nW][f], or the mean for raw None - and, for known = (init, noise, m, strength), started and blended as
-    init_video_restated.restated_loop does (m [F, h * w] or None; `latents` is then not read).  Returns float64."""
-    rows = AG.rows_for(s, s_a)
-    assert len(rows) > 1
-    _, c, F_, h, w = latents.shape
-    norm = normalised(windows, F_, raw if raw is not None else [[1.0] * len(x) for x in windows])
-    sg = D.sigmas(n)
-    euler = sampler == "euler-a"
-    b, mm = 0, None
-    if known is None:
-        lat = latents.double().clone()
-        if euler:
-            lat = lat * sg[0]
-    else:
-        init, noise, m, strength = known
-        init, noise = init.double(), noise.double()
-        b = R.begin_index(n, strength)
-        co = R.coefficients(sampler, n)
-
-        def known_at(j, last=False):
-            if last:
-                return init.clone()
-            return init + sg[j] * noise if euler else co[j][0] * init + co[j][1] * noise
-        mm = None if m is None else m.double().reshape(1, 1, F_, h, w)
-        lat = known_at(b, last=b == n)
-    guided = G.guided_steps(n - b, start, end)               # the interval counts the steps that run
-    tab = A.ddim_table(n)
-    ords = D.orders(n, begin=b)
-    hist = torch.zeros_like(lat)
-    ts = D.timesteps(n)
-    for i in range(b, n):
-        t = ts[i]
-        scale = 1.0 / math.sqrt(1.0 + sg[i] ** 2) if euler else 1.0
-        names = rows if guided[i - b] else ("c",)
-        preds = []
-        for ctx in windows:
-            trip = [AG.ROWS[r] for r in names]
-            aud = torch.cat([audio_embeddings[a][ctx] for _, _, a in trip])
-            kps = torch.stack([kps_feature[k][:, ctx] for _, k, _ in trip])
-            inp = (lat[:, :, ctx] * scale).float().repeat(len(trip), 1, 1, 1, 1)
-            out = unet_fn(inp, t, aud, kps, [bk for bk, _, _ in trip]).double()
-            p = {r: out[j:j + 1] for j, r in enumerate(names)}
-            if not guided[i - b]:
-                pred = p["c"]
-            else:
-                if names == ("u", "m", "c"):
-                    pred = p["u"] + s * (p["m"] - p["u"]) + s_a * (p["c"] - p["m"])
-                elif names == ("m", "c"):
-                    pred = p["m"] + s_a * (p["c"] - p["m"])
-                else:
-                    pred = p["u"] + s * (p["c"] - p["u"])
-                if phi > 0.0:
-                    pred = G.rescale(pred, p["c"], phi)
-            preds.append(pred)
-        x = lat.clone()
-        for fi in range(F_):
-            v = sum(wt * preds[wi][:, :, li] for wi, li, wt in norm[fi])
-            if sampler == "dpm":
-                lat[:, :, fi], hist[:, :, fi] = D.update(sg, i, ords[i - b], x[:, :, fi], v, hist[:, :, fi])
-            elif euler:
-                z = A.noise_like(seed, i, fi, c, h, w)[None]
-                lat[:, :, fi] = A.euler_a_update_ve(sg[i], sg[i + 1], x[:, :, fi], v, z)
-            else:
-                z = A.noise_like(seed, i, fi, c, h, w)[None] if sampler == "ddim-eta" else 0.0
-                a, ap = tab[i]
-                lat[:, :, fi] = A.ddim_eta_update(a, ap, eta if sampler == "ddim-eta" else 0.0, x[:, :, fi], v, z)
-        if mm is not None:
-            lat = mm * lat + (1.0 - mm) * known_at(i + 1, last=i == n - 1)
-    return lat

@@ -26,16 +26,8 @@ def run(latent=8, device="cpu", blend=BLEND):
     return lat, dict(pipe.last_schedule), dict(pipe.last_overlap)
 
 
-def main(latent=8):
-    """CPU, under RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT: this rank's final latents and its two reports."""
-    import torch.distributed as dist
-    import window_blend_restated as WB
-    from v_express_amd import ops
+def main(rank, latent=8):
+    """CPU, one rank of loop_worker.spawn_gloo: this rank's final latents and its two reports."""
     torch.set_num_threads(2)
-    dist.init_process_group("gloo")
     W.emulate_kernels()
-    ops.overlap_blend = WB.overlap_blend
-    out = run(latent)
-    dist.barrier()
-    dist.destroy_process_group()
-    return out
+    return run(latent)
