@@ -1391,3 +1391,123 @@ def test_layernorm_fold_from_two_part_statistics(ops, m, n, kind):
     frac = (got != want).float().mean().item()
     print(f"[ln fold, two-part statistics {kind} m={m} n={n}] max|diff| {diff.max().item():.4g}, differing {100 * frac:.3g} %")
     assert diff.max().item() <= 2 ** -6 * want.float().abs().max().item() and frac < 0.02
+
+
+# ------------------------------------------------------------------- the name the library gives is the kernel it launches
+# vx_gemm_config_name (what profiles and ops._on_ring key on) and vx_gemm's launch both read ONE plan (csrc/vx_gemm.hip:
+# plan_of).  One tiny problem per outcome of that plan - the smallest shapes its thresholds allow - under ops.GemmProfile,
+# whose records hold the predicted key and vx_gemm_last_kernel(): the facts the key states must be the template arguments of
+# the launched instantiation, and the output must be the product (so a launch that did nothing cannot pass).
+# case -> (expected key, LNF, GNS); the shapes are in _plan_case
+_PLAN_CASES = {
+    "256x32": ("gemm_kernel<256x32x64,4w,STORE,fast>", False, False),
+    "64x160": ("gemm_kernel<64x160x64,2w,STORE,fast>", False, False),
+    "128x160": ("gemm_kernel<128x160x64,4w,STORE,fast>", False, False),
+    "128x128": ("gemm_kernel<128x128x64,4w,STORE,fast>", False, False),
+    "256x256": ("gemm_kernel<256x256x64,8w,STORE,fast>", False, False),
+    "256x320": ("gemm_kernel<256x320x64,8w,STORE,fast>", False, False),
+    "gather": ("gemm_kernel<128x128x64,4w,STORE,gather>", False, False),
+    "gn 64x160": ("gemm_kernel<64x160x64,2w,STORE,fast>", False, True),
+    "gn 128x160": ("gemm_kernel<128x160x64,4w,STORE,fast>", False, True),
+    # enough rows for the 256 x 320 tile, which the request for GroupNorm sums takes the launch off (named 256x320 before)
+    "gn instead of 256x320": ("gemm_kernel<128x160x64,4w,STORE,fast>", False, True),
+    "split-K": ("gemm_kernel<64x160x64,2w,STORE,fast,splitk8>", False, False),
+    "ln 64x160": ("gemm_kernel<64x160x64,2w,STORE,fast>", True, False),
+    "geglu 128x128": ("gemm_kernel<128x128x64,4w,GEGLU,fast>", False, False),
+    "geglu 256x320": ("gemm_kernel<256x320x64,8w,GEGLU,fast>", False, False),
+    "split 128x160": ("gemm_kernel<128x160x64,4w,SPLIT,fast>", False, False),
+    "split 128x128": ("gemm_kernel<128x128x64,4w,SPLIT,fast>", False, False),
+    "split 256x320": ("gemm_kernel<256x320x64,8w,SPLIT,fast>", False, False),
+    "ring": ("gemm_ring_kernel<256x320x64,8w,STORE,fast>", False, False),
+    "ring geglu": ("gemm_ring_kernel<256x320x64,8w,GEGLU,fast>", False, False),
+    "ring ln": ("gemm_ring_kernel<256x320x64,8w,STORE,fast>", True, False),
+    "ring coop": ("gemm_ring_kernel<256x320x64,8w,STORE,fast,coop2>", False, False),
+    "fp8 128x160": ("gemm_kernel<128x160x128,4w,STORE,fast,fp8>", False, False),
+    "fp8 256x320": ("gemm_kernel<256x320x128,8w,STORE,fast,fp8>", False, False),
+    "fp8 split 128x160": ("gemm_kernel<128x160x128,4w,SPLIT,fast,fp8>", False, False),
+    "fp8 split 256x320": ("gemm_kernel<256x320x128,8w,SPLIT,fast,fp8>", False, False),
+    "fp8 ring": ("gemm_ring_kernel<256x320x128,8w,STORE,fast,fp8>", False, False),
+}
+_BIG_M = 65536           # 256 tiles of 256 x 320 (or 256 x 256): one per CU, from where the big classic tiles are chosen
+
+
+def _plan_case(ops, case, monkeypatch):
+    """Runs the case's launch -> (output, float64 reference, check keywords)."""
+    from v_express_amd import weights as Wt
+    if case in ("256x320", "gn instead of 256x320", "geglu 256x320"):
+        monkeypatch.setattr(ops, "RING_MODE", [0])                       # ring_hint = -1: the classic tiles
+    if case.startswith("ring") and case != "ring coop":
+        monkeypatch.setattr(ops, "_ring_hint", lambda p: 1)              # the persistent kernel whenever structurally eligible
+    if case == "ring coop":                                              # (the model's policy takes it from 4096 rows per item on)
+        monkeypatch.setattr(ops, "_ring_hint", lambda p: -1)
+        monkeypatch.setattr(ops, "ring_coop_applies", lambda p: True)
+    if case == "fp8 ring":
+        monkeypatch.setattr(ops, "FP8_RING", [True])
+    m, n, k = {"256x32": (256, 32, 64), "64x160": (128, 160, 64), "128x160": (32768, 160, 64), "128x128": (256, 128, 64),
+               "256x256": (_BIG_M, 256, 64), "256x320": (_BIG_M, 320, 64), "gn 64x160": (128, 160, 64),
+               "gn 128x160": (32768, 160, 64), "gn instead of 256x320": (_BIG_M, 320, 64), "ln 64x160": (128, 160, 64),
+               "geglu 128x128": (256, 128, 64), "geglu 256x320": (_BIG_M, 320, 64), "split 128x160": (256, 320, 64),
+               "split 128x128": (256, 128, 64), "split 256x320": (_BIG_M, 320, 64), "ring": (256, 320, 64),
+               "ring geglu": (256, 640, 64), "ring ln": (256, 320, 64), "ring coop": (256, 320, 128),
+               "fp8 128x160": (256, 320, 128), "fp8 256x320": (_BIG_M, 320, 128), "fp8 split 128x160": (256, 320, 128),
+               "fp8 split 256x320": (_BIG_M, 320, 128), "fp8 ring": (256, 320, 128)}.get(case, (0, 0, 0))
+    bias = rnd(n, seed=2, dtype=torch.float32) if n else None
+    if case == "gather":                                                 # any pad-1 3x3 at 8x8 pixels
+        x, wt, bias = rnd(2, 8, 8, 64), rnd(64, 64, 3, 3, scale=576 ** -0.5, seed=1), rnd(64, seed=2, dtype=torch.float32)
+        out = ops.gemm(x.view(-1, 64), wt.permute(0, 2, 3, 1).reshape(64, -1).contiguous(), bias, geom=ops.ConvGeom(2, 8, 8, 3, 3, 1, 1))
+        return out, _conv_ref(x, wt, bias, 1, 1, 0).reshape(-1, 64), {}
+    if case == "split-K":                                                # the 8x8-level K >= 2560 conv of test_gemm_split_k
+        x, wt, bias = rnd(6, 10, 10, 320), rnd(320, 320, 3, 3, scale=2880 ** -0.5, seed=1), rnd(320, seed=2, dtype=torch.float32)
+        out = ops.gemm(x.view(-1, 320), wt.permute(0, 2, 3, 1).reshape(320, -1).contiguous(), bias, geom=ops.ConvGeom(6, 10, 10, 3, 3, 1, 0))
+        return out, _conv_ref(x, wt, bias, 1, 0, 0).reshape(-1, 320), {}
+    a, w = rnd(m, k), rnd(n, k, scale=k ** -0.5, seed=1)
+    if case.startswith("fp8"):
+        a, w = ops.quantize_fp8(a), ops.fp8_weight(w)
+        ref = _deq(a.q, a.scale).double() @ _deq(w.w8, w.scale).double().t() + bias.double()
+    else:
+        ref = a.double() @ w.double().t() + bias.double()
+    if "split" in case:
+        out = torch.zeros(m, n, device="cuda", dtype=BF)
+        ops.gemm_split(a, w, bias, [("rows", out)], part_cols=n)
+        return out, ref, {}
+    if "geglu" in case:
+        out = ops.geglu(a, Wt.geglu_interleave(w), Wt.geglu_interleave(bias))
+        return out, ref[:, :n // 2] * F.gelu(ref[:, n // 2:]), {}
+    if "ln" in case:
+        gamma, beta = 1 + 0.1 * rnd(k, seed=4, dtype=torch.float32), 0.1 * rnd(k, seed=5, dtype=torch.float32)
+        Fd = _folded(ops, w, bias, gamma, beta)
+        ref = F.layer_norm(a.double(), (k,), gamma.double(), beta.double(), 1e-5) @ w.double().t() + bias.double()
+        return ops.gemm(a, Fd.w, Fd.b, ln=(ops.row_stats(a), Fd.s)), ref, dict(rel=8e-3, mx=2 ** -6)
+    if case.startswith("gn"):
+        out = ops.gemm(a, w, bias, gn=(32, 64))
+        assert ops.gn_of(out) is not None and ops.gn_of(out).slabs == 1
+        return out, ref, {}
+    return ops.gemm(a, w, bias), ref, {}
+
+
+@pytest.mark.parametrize("case", sorted(_PLAN_CASES))
+def test_gemm_config_name_is_the_kernel_launched(ops, monkeypatch, case):
+    import re
+    key, lnf, gns = _PLAN_CASES[case]
+    with ops.GemmProfile() as prof:
+        out, ref, tol = _plan_case(ops, case, monkeypatch)
+    recs = [r for r in prof.records if len(r) == 7 and isinstance(r[4], tuple)]        # (the GEMM launches: ln adds row_stats)
+    assert len(recs) == 1 and recs[0][3] == key, [r[3] for r in recs]
+    sym = recs[0][5]
+    fam, bm, bn, bk, waves, epi, addr, f8, split = re.fullmatch(
+        r"(gemm_ring_kernel|gemm_kernel)<(\d+)x(\d+)x(\d+),(\d+)w,(STORE|GEGLU|SPLIT),(fast|gather)(,fp8)?(?:,(splitk\d+|coop2))?>",
+        key).groups()
+    said = dict(ring=fam == "gemm_ring_kernel", tile=(int(bm), int(bn)), waves=int(waves), fast=addr == "fast", f8=bool(f8),
+                epi=("STORE", "GEGLU", "SPLIT").index(epi), coop=split == "coop2", lnf=lnf, gns=gns)
+    assert int(bk) == (128 if f8 else 64)
+    name, args = sym[:-1].split("<")
+    args = [a.strip() == "true" if a.strip() in ("true", "false") else int(a) for a in args.split(",")]
+    if name == "gemm_ring_kernel":        # <EPI, RES, F8, STATS, LNF, GNS[, SK]>: always the 256 x 320 tile, 8 waves, FAST addressing
+        ran = dict(ring=True, tile=(256, 320), waves=8, fast=True, f8=args[2], epi=args[0], coop=len(args) > 6 and args[6],
+                   lnf=args[4], gns=args[5])
+    else:                                 # <BM, BN, WARPS_M, WARPS_N, STAGES, EPI, FAST, F8, LNF, GNS>
+        assert name == "gemm_kernel"
+        ran = dict(ring=False, tile=(args[0], args[1]), waves=args[2] * args[3], fast=args[6], f8=args[7], epi=args[5],
+                   coop=False, lnf=args[8], gns=args[9])
+    assert said == ran, (key, sym)
+    check(out, ref.float(), f"{'fp8 ' if f8 else ''}plan outcome {case}", **tol)

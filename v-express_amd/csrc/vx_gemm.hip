@@ -699,13 +699,32 @@ int launch_impl(const vx_gemm_params& p, hipStream_t stream) {
   return vx_check_launch("vx_gemm(split-K reduce)");
 }
 
-// FAST-path eligibility (see gemm_kernel)
-bool fast_ok(const vx_gemm_params& p) { return vx_gemm_fast_ok(p); }
+// A/B knobs of the kernel choice (benchmarking only; environment, read once at first use)
+struct Knobs {
+  int tile;              // VX_GEMM_TILE=big|small: the 256 x 320 tile always / never (for n % 320 == 0); else by tile count
+  bool small64;          // VX_GEMM_SMALL64=0: no 64 x 160 tile
+  long small64_below;    // VX_GEMM_SMALL64_BELOW: the 64-row tile is used while the 128-row tiling has fewer blocks (256)
+  bool t256x256;         // VX_GEMM_T256X256=0: the 256- / 512-channel convolutions stay on the 128 x 128 tile
+  bool t128x320;         // VX_GEMM_T128X320=1 (experiment, round 4): n % 320 == 0 launches too small for 256 x 320 on 128 x 320
+  int stages128;         // VX_GEMM_STAGES128 = 2 | 3 | 4: pipeline depth of the 128 x 160 tile
+  bool nofast;           // VX_GEMM_NOFAST: no FAST addressing anywhere
+};
+enum { CFG_AUTO = 0, CFG_BIG = 1, CFG_SMALL = 2 };
+const Knobs& knobs() {
+  static const Knobs k = [] {
+    auto is = [](const char* name, const char* v) { const char* e = getenv(name); return e && !strcmp(e, v); };
+    const char *below = getenv("VX_GEMM_SMALL64_BELOW"), *st = getenv("VX_GEMM_STAGES128");
+    return Knobs{is("VX_GEMM_TILE", "big") ? CFG_BIG : is("VX_GEMM_TILE", "small") ? CFG_SMALL : CFG_AUTO,
+                 !is("VX_GEMM_SMALL64", "0"), below ? atol(below) : 256, !is("VX_GEMM_T256X256", "0"),
+                 is("VX_GEMM_T128X320", "1"), st ? atoi(st) : 2, getenv("VX_GEMM_NOFAST") != nullptr};
+  }();
+  return k;
+}
 }  // namespace
+
+// FAST-path eligibility (see gemm_kernel)
 bool vx_gemm_fast_ok(const vx_gemm_params& p) {
-  static int disabled = -1;
-  if (disabled < 0) disabled = getenv("VX_GEMM_NOFAST") != nullptr;
-  if (disabled) return false;
+  if (knobs().nofast) return false;
   const int cin = p.c1 + p.c2;
   const unsigned long long rows_in = (unsigned long long)p.nb * p.h_in * p.w_in;
   return p.pad == 0 && p.upsample == 0 && (cin % 64) == 0 && (p.c1 % 64) == 0 && (p.k % 64) == 0 &&
@@ -716,137 +735,163 @@ bool vx_gemm_fast_ok(const vx_gemm_params& p) {
 }
 namespace {
 
-template <int BM, int BN, int WARPS_M, int WARPS_N, int STAGES, int EPI>
-int launch(const vx_gemm_params& p, hipStream_t stream) {
-  if (p.ln_stats != nullptr) {
-    if (!fast_ok(p)) {
-      vx_set_error("vx_gemm: a folded LayerNorm needs a plain linear (k %% 64 == 0, no padding / upsampling)");
-      return VX_ERR_UNSUPPORTED;
-    }
-    return launch_impl<BM, BN, WARPS_M, WARPS_N, STAGES, EPI, true, false, true>(p, stream);
-  }
-  if (fast_ok(p)) return launch_impl<BM, BN, WARPS_M, WARPS_N, STAGES, EPI, true>(p, stream);
-  return launch_impl<BM, BN, WARPS_M, WARPS_N, STAGES, EPI, false>(p, stream);
-}
+// The kernel choice is stated ONCE, in plan_of: vx_gemm launches the plan, vx_gemm_config_name prints it, vx_gemm_gn_slabs
+// and vx_gemm_ring_coop_ok read it.  (The variant of the persistent kernel - RES / STATS / LNF / GNS / SK: vx_gemm_ring_launch.)
+enum { T_256x32 = 0, T_BIG, T_SMALL64, T_128x160, T_128x128, T_128x320, T_256x256, T_COUNT };
+const struct { int bm, bn, warps_m, warps_n; const char *text, *text_f8; } TILES[T_COUNT] = {
+    {256, 32, 4, 1, "256x32x64,4w", nullptr},
+    // one block per CU: A is streamed once for N = 320 and a K-tile's DMA (72 KiB) is covered by 2x the MFMA work of the
+    // 128-row tiles.  Also the persistent ring kernel's tile (R_BM x R_BN of vx_gemm_ring.hip).
+    {256, 320, 4, 2, "256x320x64,8w", "256x320x128,8w"},
+    // 2 waves, 3 stages: launches whose 128-row tiling would leave CUs without a block (the 8x8 level of a 16-frame window:
+    // M = 2048 -> 128 tiles of 128 x 160 for N = 1280)
+    {64, 160, 1, 2, "64x160x64,2w", nullptr},
+    // (VX_GEMM_STAGES128: 8192 x 1280 x 1280 is DMA-latency bound at depth 2, 2 us per K-tile against 0.3 us of MFMA work)
+    {128, 160, 2, 2, "128x160x64,4w", "128x160x128,4w"},
+    {128, 128, 2, 2, "128x128x64,4w", nullptr},
+    // one block per CU: 10.9 KB of operands per MFLOP through the CU's L1 instead of the 128 x 160 tile's 14.1
+    {128, 320, 2, 4, "128x320x64,8w", nullptr},
+    // wave 64 x 128, one block per CU: the VAE decoder's 256- and 512-channel convolutions (M = 65536 ... 1048576 rows):
+    // 7.8 KB of operands per MFLOP through the CU's L1 instead of the 128 x 128 tile's 15.6
+    {256, 256, 4, 2, "256x256x64,8w", nullptr},
+};
+// Which tile a launch gets never changes its results: every tile shape accumulates an output element over the K-tiles in
+// the same order with the same MFMA (the persistent kernel walks conv taps innermost: other fp32 summation order).
 
-// STORE launch that also writes GroupNorm partial sums (p.gn_ws): instantiated for the tiles the 16x16 / 8x8 levels use
-template <int BM, int BN, int WARPS_M, int WARPS_N, int STAGES>
-int launch_gns(const vx_gemm_params& p, hipStream_t stream) {
-  if (fast_ok(p)) return launch_impl<BM, BN, WARPS_M, WARPS_N, STAGES, VX_EPI_STORE, true, false, false, true>(p, stream);
-  return launch_impl<BM, BN, WARPS_M, WARPS_N, STAGES, VX_EPI_STORE, false, false, false, true>(p, stream);
-}
+struct GemmPlan {
+  bool ring;       // the persistent ring-staged kernel (vx_gemm_ring.hip; tile = T_BIG) instead of gemm_kernel<tile, ...>
+  int tile, stages;   // T_*; pipeline depth (classic tiles)
+  bool fast;       // FAST addressing; else the gathering loads
+  bool f8, lnf;    // fp8 operands; a folded LayerNorm (p.ln_stats)
+  bool gns;        // the epilogue writes GroupNorm partial sums (classic tiles: 64 rows per slab)
+  int splitk;      // 1 = off; with ring: 2 = the cooperative two-way split
+  int epi;         // VX_EPI_*
+};
 
+// at least one 256 x 320 tile per CU
+bool fills_cus_256x320(const vx_gemm_params& p) { return (p.n % 320) == 0 && (long)ceil_div(p.m, 256) * (p.n / 320) >= 256; }
+bool use_big(const vx_gemm_params& p) {
+  if ((p.n % 320) != 0 || p.splitk > 1) return false;   // split-K wants many small tiles
+  return knobs().tile == CFG_BIG || (knobs().tile == CFG_AUTO && fills_cus_256x320(p));
+}
 // column-tile width with the least padding (ties -> 160: fewer, fatter tiles)
 bool prefer160(int n) {
   int w160 = ceil_div(n, 160) * 160 - n, w128 = ceil_div(n, 128) * 128 - n;
   return w160 * 128 <= w128 * 160;
 }
-
-// Tile configuration.  BIG = 256x320 tile, 8 waves, one block per CU: A is streamed once for N = 320 and a
-// K-tile's DMA (72 KiB) is covered by 2x the MFMA work of the 128-row tiles -> used when N is a multiple of 320 and
-// the launch still has >= 1 tile per CU.  VX_GEMM_TILE=big|small|small3 overrides (benchmarking only).
-enum { CFG_AUTO = 0, CFG_BIG = 1, CFG_SMALL = 2 };
-int forced_cfg() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("VX_GEMM_TILE");
-    v = CFG_AUTO;
-    if (e && !strcmp(e, "big")) v = CFG_BIG;
-    if (e && !strcmp(e, "small")) v = CFG_SMALL;
-  }
-  return v;
-}
-bool use_big(const vx_gemm_params& p) {
-  if ((p.n % 320) != 0 || p.splitk > 1) return false;   // split-K wants many small tiles
-  int f = forced_cfg();
-  if (f == CFG_BIG) return true;
-  if (f == CFG_SMALL) return false;
-  long tiles = (long)ceil_div(p.m, 256) * (p.n / 320);
-  return tiles >= 256;
-}
-
-// 64 x 160 tile, 2 waves, 3 stages: launches whose 128-row tiling would leave CUs without a block (the 8x8 level of a
-// 16-frame window: M = 2048 -> 128 tiles of 128 x 160 for N = 1280).  Which tile a launch gets never changes its
-// results: every tile shape accumulates an output element over the K-tiles in the same order with the same MFMA.
-// VX_GEMM_SMALL64=0 disables (A/B measurements).
 bool use_small64(const vx_gemm_params& p) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("VX_GEMM_SMALL64");
-    on = !(e && !strcmp(e, "0"));
-  }
-  if (!on || !prefer160(p.n) || p.out_f32) return false;
+  if (!knobs().small64 || !prefer160(p.n) || p.out_f32) return false;
   const long tiles128 = (long)ceil_div(p.m, 128) * ceil_div(p.n, 160) * (p.splitk > 1 ? p.splitk : 1);
-  static long lim = -1;   // VX_GEMM_SMALL64_BELOW (A/B knob): the 64-row tile is used while the 128-row tiling has fewer blocks
-  if (lim < 0) {
-    const char* e = getenv("VX_GEMM_SMALL64_BELOW");
-    lim = e ? atol(e) : 256;
-  }
-  return tiles128 < lim && fast_ok(p);
+  return tiles128 < knobs().small64_below && vx_gemm_fast_ok(p);
 }
-
-// which classic tile a bf16-operand STORE launch gets (the persistent ring kernel is asked first by the callers)
-enum { T_256x32 = 0, T_BIG, T_SMALL64, T_128x160, T_128x128, T_128x320, T_256x256 };
-// 256 x 256 tile, 8 waves as 4 x 2 (wave 64 x 128), one block per CU: the VAE decoder's 256- and 512-channel convolutions
-// (M = 65536 ... 1048576 rows): 7.8 KB of operands per MFLOP through the CU's L1 instead of the 128 x 128 tile's 15.6.
-// VX_GEMM_T256X256=0 keeps them on the 128 x 128 tile (A/B knob).
-bool use_256x256(const vx_gemm_params& p) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("VX_GEMM_T256X256");
-    on = !(e && !strcmp(e, "0"));
-  }
-  return on && (p.n % 256) == 0 && p.n <= 1024 && p.splitk <= 1 && !p.out_f32 && (long)ceil_div(p.m, 256) * (p.n / 256) >= 256;
-}
-// VX_GEMM_T128X320=1 (experiment, round 4): the 16x16-level launches (n % 320 == 0, too few 256-row tiles for the big
-// kernels) on a 128 x 320 tile, 8 waves as 2 x 4, one block per CU: 10.9 KB of operands per MFLOP through the CU's L1
-// instead of the 128 x 160 tile's 14.1
-bool use_128x320(const vx_gemm_params& p) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("VX_GEMM_T128X320");
-    on = e && !strcmp(e, "1");
-  }
-  return on && (p.n % 320) == 0 && p.splitk <= 1 && !p.out_f32;
-}
-// gn: the launch is asked for GroupNorm partial sums (vx_gemm_params.gn_ws).  Only the 64-row-per-wave 64 x 160 and
-// 128 x 160 tiles produce them, and WHETHER a launch produces them must not depend on how many frames share it (the sums
-// then come from a differently grouped statistics pass: other bits) - so a request for them takes the launch off the
-// 256 x 320 tile, whose use depends on the row count.
-int store_tile(const vx_gemm_params& p, bool gn = false) {
+// the classic tile of a bf16-operand STORE launch.  gn: the launch is asked for GroupNorm partial sums.  Only the
+// 64-row-per-wave 64 x 160 and 128 x 160 tiles produce them, and WHETHER a launch produces them must not depend on how many
+// frames share it (the sums then come from a differently grouped statistics pass: other bits) - so a request for them takes
+// the launch off the 256 x 320 tile, whose use depends on the row count.
+int store_tile(const vx_gemm_params& p, bool gn) {
   if (p.n <= 32) return T_256x32;
   if (gn && (p.n % 160) == 0) return use_small64(p) ? T_SMALL64 : T_128x160;
   if (use_big(p)) return T_BIG;
   if (use_small64(p)) return T_SMALL64;
-  if (use_128x320(p)) return T_128x320;
+  if (knobs().t128x320 && (p.n % 320) == 0 && p.splitk <= 1 && !p.out_f32) return T_128x320;
   if (prefer160(p.n)) return T_128x160;
-  if (use_256x256(p)) return T_256x256;
+  const bool fills_cus_256x256 = (p.n % 256) == 0 && p.n <= 1024 && (long)ceil_div(p.m, 256) * (p.n / 256) >= 256;
+  if (knobs().t256x256 && fills_cus_256x256 && p.splitk <= 1 && !p.out_f32) return T_256x256;
   return T_128x128;
+}
+
+// gn_requested: p.gn_ws != nullptr for a launch and for its name; true for the question vx_gemm_gn_slabs answers
+GemmPlan plan_of(const vx_gemm_params& p, bool gn_requested) {
+  GemmPlan pl = {};
+  pl.epi = p.epi;
+  pl.f8 = p.a_fp8 != 0;
+  pl.fast = pl.f8 || vx_gemm_fast_ok(p);   // (fp8: plain linears only)
+  pl.lnf = p.ln_stats != nullptr;
+  pl.splitk = (!pl.f8 && p.splitk > 1) ? p.splitk : 1;
+  pl.ring = vx_gemm_ring_eligible(p);
+  if (pl.ring) pl.tile = T_BIG;
+  else if (pl.f8) pl.tile = fills_cus_256x320(p) ? T_BIG : T_128x160;
+  else if (p.epi == VX_EPI_STORE) pl.tile = store_tile(p, gn_requested);
+  else if (use_big(p)) pl.tile = T_BIG;
+  else pl.tile = (p.epi != VX_EPI_GEGLU && prefer160(p.n)) ? T_128x160 : T_128x128;
+  const bool store = p.epi == VX_EPI_STORE && !pl.f8 && !pl.ring;   // a bf16 STORE launch on the classic tiles
+  pl.stages = pl.tile == T_SMALL64 ? 3 : (pl.tile == T_128x160 && store) ? knobs().stages128 : 2;
+  // (the A/B depth knob has no partial-sum instantiation)
+  pl.gns = gn_requested && (pl.ring || (store && (p.n % 160) == 0 && p.splitk <= 1 && (pl.tile == T_SMALL64 || pl.stages == 2)));
+  return pl;
+}
+
+template <int BM, int BN, int WARPS_M, int WARPS_N, int STAGES, int EPI>
+int launch(const vx_gemm_params& p, const GemmPlan& pl, hipStream_t stream) {
+  if (pl.lnf) {
+    if (!pl.fast) {
+      vx_set_error("vx_gemm: a folded LayerNorm needs a plain linear (k %% 64 == 0, no padding / upsampling)");
+      return VX_ERR_UNSUPPORTED;
+    }
+    return launch_impl<BM, BN, WARPS_M, WARPS_N, STAGES, EPI, true, false, true>(p, stream);
+  }
+  if (pl.fast) return launch_impl<BM, BN, WARPS_M, WARPS_N, STAGES, EPI, true>(p, stream);
+  return launch_impl<BM, BN, WARPS_M, WARPS_N, STAGES, EPI, false>(p, stream);
+}
+
+// STORE launch that also writes GroupNorm partial sums (p.gn_ws): instantiated for the tiles the 16x16 / 8x8 levels use
+template <int BM, int BN, int WARPS_M, int WARPS_N, int STAGES>
+int launch_gns(const vx_gemm_params& p, const GemmPlan& pl, hipStream_t stream) {
+  if (pl.fast) return launch_impl<BM, BN, WARPS_M, WARPS_N, STAGES, VX_EPI_STORE, true, false, false, true>(p, stream);
+  return launch_impl<BM, BN, WARPS_M, WARPS_N, STAGES, VX_EPI_STORE, false, false, false, true>(p, stream);
+}
+
+// the plan -> its instantiation (every gemm_kernel<> the library holds is named here, and only here)
+int launch_plan(const vx_gemm_params& p, const GemmPlan& pl, hipStream_t stream) {
+  if (pl.ring) return vx_gemm_ring_launch(p, stream);
+  constexpr int STORE = VX_EPI_STORE, GEGLU = VX_EPI_GEGLU, SPLIT = VX_EPI_SPLIT;
+  constexpr auto key = [](int epi, int tile) { return epi * T_COUNT + tile; };
+  switch (key(pl.epi, pl.tile)) {
+    case key(STORE, T_256x32): return launch<256, 32, 4, 1, 2, STORE>(p, pl, stream);
+    case key(STORE, T_128x320): return launch<128, 320, 2, 4, 2, STORE>(p, pl, stream);
+    case key(STORE, T_256x256): return launch<256, 256, 4, 2, 2, STORE>(p, pl, stream);
+    case key(STORE, T_128x128): return launch<128, 128, 2, 2, 2, STORE>(p, pl, stream);
+    case key(STORE, T_BIG):
+      if (pl.f8) return launch_impl<256, 320, 4, 2, 2, STORE, true, true>(p, stream);
+      return launch<256, 320, 4, 2, 2, STORE>(p, pl, stream);
+    case key(STORE, T_SMALL64):
+      if (pl.gns) return launch_gns<64, 160, 1, 2, 3>(p, pl, stream);
+      return launch<64, 160, 1, 2, 3, STORE>(p, pl, stream);
+    case key(STORE, T_128x160):
+      if (pl.f8) return launch_impl<128, 160, 2, 2, 2, STORE, true, true>(p, stream);
+      if (pl.gns) return launch_gns<128, 160, 2, 2, 2>(p, pl, stream);
+      if (pl.stages == 3) return launch<128, 160, 2, 2, 3, STORE>(p, pl, stream);
+      if (pl.stages == 4) return launch<128, 160, 2, 2, 4, STORE>(p, pl, stream);
+      return launch<128, 160, 2, 2, 2, STORE>(p, pl, stream);
+    case key(GEGLU, T_BIG): return launch<256, 320, 4, 2, 2, GEGLU>(p, pl, stream);
+    case key(GEGLU, T_128x128): return launch<128, 128, 2, 2, 2, GEGLU>(p, pl, stream);
+    case key(SPLIT, T_BIG):
+      if (pl.f8) return launch_impl<256, 320, 4, 2, 2, SPLIT, true, true>(p, stream);
+      return launch<256, 320, 4, 2, 2, SPLIT>(p, pl, stream);
+    case key(SPLIT, T_128x160):
+      if (pl.f8) return launch_impl<128, 160, 2, 2, 2, SPLIT, true, true>(p, stream);
+      return launch<128, 160, 2, 2, 2, SPLIT>(p, pl, stream);
+    case key(SPLIT, T_128x128): return launch<128, 128, 2, 2, 2, SPLIT>(p, pl, stream);
+  }
+  vx_set_error("vx_gemm: no kernel for epilogue %d on tile %s", pl.epi, TILES[pl.tile].text);
+  return VX_ERR_UNSUPPORTED;
 }
 
 }  // namespace
 
 // GroupNorm partial sums from the STORE epilogue (vx_gemm_params.gn_ws): slabs per frame the launch of p writes, 0 = it
-// cannot (the caller keeps the separate statistics pass).  Mirrors vx_gemm_dispatch's kernel choice.
+// cannot (the caller keeps the separate statistics pass)
 extern "C" int vx_gemm_gn_slabs(const vx_gemm_params* pp) {
   const vx_gemm_params& p = *pp;
   if (p.epi != VX_EPI_STORE || p.a_fp8 || p.out_f32 || p.ln_stats != nullptr || p.row_stats_out != nullptr ||
       (p.splitk > 1 && p.ring_hint != 2) || p.w_group_rows != 0)
     return 0;
   if (p.gn_groups <= 0 || p.gn_hw <= 0 || p.n <= 0 || (p.n % p.gn_groups) != 0 || (p.m % p.gn_hw) != 0) return 0;
-  if (vx_gemm_ring_eligible(p)) return vx_gemm_ring_gn_slabs(p);
-  if (p.splitk > 1) return 0;
+  const GemmPlan pl = plan_of(p, true);
+  if (pl.ring) return vx_gemm_ring_gn_slabs(p);
+  if (!pl.gns) return 0;
   const int cg = p.n / p.gn_groups;
-  const int tile = store_tile(p, true);
-  if (tile != T_SMALL64 && tile != T_128x160) return 0;
-  static int st128 = -1;
-  if (st128 < 0) {
-    const char* e = getenv("VX_GEMM_STAGES128");
-    st128 = e ? atoi(e) : 2;
-  }
-  if (tile == T_128x160 && st128 != 2) return 0;   // (the A/B depth knob has no partial-sum instantiation)
-  const int bm = tile == T_SMALL64 ? 64 : 128;
-  if ((p.m % bm) != 0 || (p.n % 160) != 0 || (p.gn_hw % 64) != 0 || (80 % cg) != 0) return 0;   // whole tiles, wave = 64 x 80
+  if ((p.m % TILES[pl.tile].bm) != 0 || (p.gn_hw % 64) != 0 || (80 % cg) != 0) return 0;   // whole tiles, wave = 64 x 80
   return p.gn_hw / 64;
 }
 
@@ -861,7 +906,7 @@ extern "C" int vx_gemm_ring_coop_ok(const vx_gemm_params* pp) {
   q.ring_hint = 2;
   q.splitk = 2;
   if (q.splitk_ws == nullptr) q.splitk_ws = (void*)16;   // (only tested for null)
-  return vx_gemm_ring_eligible(q) ? 1 : 0;
+  return plan_of(q, q.gn_ws != nullptr).ring ? 1 : 0;
 }
 
 extern "C" int64_t vx_gemm_splitk_ws_bytes(int m, int n, int splitk) {
@@ -869,33 +914,14 @@ extern "C" int64_t vx_gemm_splitk_ws_bytes(int m, int n, int splitk) {
 }
 
 extern "C" const char* vx_gemm_config_name(const vx_gemm_params* pp) {
-  const vx_gemm_params& p = *pp;
-  const bool fast = fast_ok(p);
-  const char* epi = p.epi == VX_EPI_STORE ? "STORE" : (p.epi == VX_EPI_GEGLU ? "GEGLU" : "SPLIT");
-  const char* tile;
-  if (p.a_fp8) {
-    static thread_local char b8[96];
-    if (p.epi == VX_EPI_STORE && vx_gemm_ring_eligible(p)) return "gemm_ring_kernel<256x320x128,8w,STORE,fast,fp8>";
-    const bool big8 = (p.n % 320) == 0 && (long)ceil_div(p.m, 256) * (p.n / 320) >= 256;
-    snprintf(b8, sizeof(b8), "gemm_kernel<%s,%s,fast,fp8>", big8 ? "256x320x128,8w" : "128x160x128,4w", epi);
-    return b8;
-  }
-  if (vx_gemm_ring_eligible(p))
-    return p.epi == VX_EPI_GEGLU ? "gemm_ring_kernel<256x320x64,8w,GEGLU,fast>"
-                                 : (p.ring_hint == 2 ? "gemm_ring_kernel<256x320x64,8w,STORE,fast,coop2>"
-                                                     : "gemm_ring_kernel<256x320x64,8w,STORE,fast>");
-  if (p.epi == VX_EPI_STORE && p.n <= 32) tile = "256x32x64,4w";
-  else if (use_big(p)) tile = "256x320x64,8w";
-  else if (p.epi == VX_EPI_STORE && use_small64(p)) tile = "64x160x64,2w";
-  else if (p.epi == VX_EPI_STORE && use_128x320(p)) tile = "128x320x64,8w";
-  else if (p.epi == VX_EPI_STORE && !prefer160(p.n) && use_256x256(p)) tile = "256x256x64,8w";
-  else if (p.epi != VX_EPI_GEGLU && prefer160(p.n)) tile = "128x160x64,4w";
-  else tile = "128x128x64,4w";
+  const GemmPlan pl = plan_of(*pp, pp->gn_ws != nullptr);
+  const char* epi = pl.epi == VX_EPI_STORE ? "STORE" : (pl.epi == VX_EPI_GEGLU ? "GEGLU" : "SPLIT");
+  char split[16] = "";
+  if (pl.splitk > 1 && pl.ring) snprintf(split, sizeof(split), ",coop2");
+  else if (pl.splitk > 1) snprintf(split, sizeof(split), ",splitk%d", pl.splitk);
   static thread_local char buf[96];
-  if (p.splitk > 1)
-    snprintf(buf, sizeof(buf), "gemm_kernel<%s,%s,%s,splitk%d>", tile, epi, fast ? "fast" : "gather", p.splitk);
-  else
-    snprintf(buf, sizeof(buf), "gemm_kernel<%s,%s,%s>", tile, epi, fast ? "fast" : "gather");
+  snprintf(buf, sizeof(buf), "%s<%s,%s,%s%s%s>", pl.ring ? "gemm_ring_kernel" : "gemm_kernel",
+           pl.f8 ? TILES[pl.tile].text_f8 : TILES[pl.tile].text, epi, pl.fast ? "fast" : "gather", pl.f8 ? ",fp8" : "", split);
   return buf;
 }
 
@@ -904,13 +930,14 @@ static int vx_gemm_dispatch(const vx_gemm_params& p, hipStream_t stream);
 extern "C" int vx_gemm(const vx_gemm_params* pp, void* stream_) {
   const vx_gemm_params& p = *pp;
   hipStream_t stream = (hipStream_t)stream_;
+  auto on_ring = [&p] { return plan_of(p, p.gn_ws != nullptr).ring; };
   if (p.row_stats_out != nullptr)
     VX_REQUIRE(p.epi == VX_EPI_STORE && !p.out_f32 && p.row_stats_eps > 0.f && p.out != nullptr,
                "vx_gemm: row_stats_out needs the STORE epilogue into bf16 and row_stats_eps > 0");
   VX_REQUIRE(p.row_stats_parts == 0 || p.row_stats_parts == 1 || (p.row_stats_parts == 2 && p.n == 640),
              "vx_gemm: row_stats_parts=%d (0 / 1, or 2 with n == 640; n=%d)", p.row_stats_parts, p.n);
   if (p.ln_stats != nullptr && p.ln_stats_parts == 2) {
-    if (p.k != 640 || !(p.ln_eps > 0.f) || !vx_gemm_ring_eligible(p)) {
+    if (p.k != 640 || !(p.ln_eps > 0.f) || !on_ring()) {
       vx_set_error("vx_gemm: ln_stats_parts = 2 needs k == 640, ln_eps > 0 and a launch on the persistent kernel (k=%d m=%d "
                    "n=%d): convert with vx_row_stats_finalize", p.k, p.m, p.n);
       return VX_ERR_UNSUPPORTED;
@@ -929,7 +956,7 @@ extern "C" int vx_gemm(const vx_gemm_params* pp, void* stream_) {
   }
   const int rc = vx_gemm_dispatch(p, stream);
   if (rc != VX_OK || p.row_stats_out == nullptr) return rc;
-  if (vx_gemm_ring_eligible(p) && vx_gemm_ring_writes_row_stats(p)) return rc;   // the epilogue wrote them
+  if (on_ring() && vx_gemm_ring_writes_row_stats(p)) return rc;   // the epilogue wrote them
   if (p.row_stats_parts == 2) return vx_row_stats_parts(p.out, p.ldc, p.m, p.n, p.row_stats_out, stream_);
   return vx_row_stats(p.out, p.ldc, p.m, p.n, p.row_stats_eps, p.row_stats_out, stream_);
 }
@@ -952,6 +979,7 @@ static int vx_gemm_dispatch(const vx_gemm_params& p, hipStream_t stream) {
   VX_REQUIRE(p.splitk <= 1 || (p.epi == VX_EPI_STORE && p.splitk_ws != nullptr && p.splitk <= 16 &&
                                p.splitk <= (p.k + BK - 1) / BK),
              "vx_gemm: split-K needs the STORE epilogue, a workspace and splitk <= min(16, K/64)");
+  const GemmPlan pl = plan_of(p, p.gn_ws != nullptr);
   if (p.a_fp8) {
     // fp8 projections: plain linears over zero-padded K (see vx_gemm_params.a_fp8)
     VX_REQUIRE(p.a_scale != nullptr && p.w_scale != nullptr, "vx_gemm(fp8): null scale table");
@@ -963,66 +991,29 @@ static int vx_gemm_dispatch(const vx_gemm_params& p, hipStream_t stream) {
     VX_REQUIRE((unsigned long long)p.m * p.lda1 < (1ull << 32) && (unsigned long long)p.n * p.k < (1ull << 32),
                "vx_gemm(fp8): operand spans 4 GiB");
     VX_REQUIRE(p.epi == VX_EPI_STORE || p.epi == VX_EPI_SPLIT, "vx_gemm(fp8): STORE / SPLIT epilogues only");
-    const bool big = (p.n % 320) == 0 && (long)ceil_div(p.m, 256) * (p.n / 320) >= 256;
-    if (p.epi == VX_EPI_STORE) {
-      VX_REQUIRE(p.out != nullptr && (p.ldc % 8) == 0, "vx_gemm: STORE needs out and ldc%%8==0");
-      VX_REQUIRE(p.residual == nullptr || (p.ldr % 8) == 0, "vx_gemm: ldr%%8");
-      VX_REQUIRE(p.rowbias == nullptr || p.rows_per_group > 0, "vx_gemm: rows_per_group");
-      if (vx_gemm_ring_eligible(p)) return vx_gemm_ring_launch(p, stream);
-      if (big) return launch_impl<256, 320, 4, 2, 2, VX_EPI_STORE, true, true>(p, stream);
-      return launch_impl<128, 160, 2, 2, 2, VX_EPI_STORE, true, true>(p, stream);
-    }
   }
   if (p.epi == VX_EPI_STORE) {
     VX_REQUIRE(p.out != nullptr && (p.ldc % 8) == 0, "vx_gemm: STORE needs out and ldc%%8==0");
     VX_REQUIRE(p.residual == nullptr || (p.ldr % 8) == 0, "vx_gemm: ldr%%8");
     VX_REQUIRE(p.rowbias == nullptr || p.rows_per_group > 0, "vx_gemm: rows_per_group");
-    if (p.ring_hint == 2 && (p.coop_epoch < 1 || p.coop_epoch >= (1 << 27))) {
+    if (!p.a_fp8 && p.ring_hint == 2 && (p.coop_epoch < 1 || p.coop_epoch >= (1 << 27))) {
       vx_set_error("vx_gemm: ring_hint = 2 needs 1 <= coop_epoch < 2^27 (the workspace's launch counter), got %d", p.coop_epoch);
       return VX_ERR_INVALID;
     }
-    if (vx_gemm_ring_eligible(p)) return vx_gemm_ring_launch(p, stream);
-    if (p.ring_hint == 2) {
+    if (!pl.ring && !p.a_fp8 && p.ring_hint == 2) {
       vx_set_error("vx_gemm: ring_hint = 2 (cooperative two-way K split on the persistent kernel) needs splitk == 2, a zeroed "
                    "workspace, m %% 256 == 0, n %% 320 == 0, an even number of 64-channel chunks and the plain STORE epilogue "
                    "(m=%d n=%d k=%d splitk=%d): ask vx_gemm_ring_coop_ok() first", p.m, p.n, p.k, p.splitk);
       return VX_ERR_UNSUPPORTED;
     }
-    if (p.w_group_rows != 0) {
+    if (!pl.ring && p.w_group_rows != 0) {
       vx_set_error("vx_gemm: per-row-group weights (w_group_rows=%d) need a launch the persistent 256 x 320 kernel "
                    "accepts (m %% 256, n %% 320, w_group_rows %% 256, plain addressing)", p.w_group_rows);
       return VX_ERR_UNSUPPORTED;
     }
-    const int tile = store_tile(p, p.gn_ws != nullptr);
-    if (p.gn_ws != nullptr) {
-      // (vx_gemm checked vx_gemm_gn_slabs(p) > 0: only these two tiles produce the partial sums)
-      if (tile == T_SMALL64) return launch_gns<64, 160, 1, 2, 3>(p, stream);
-      return launch_gns<128, 160, 2, 2, 2>(p, stream);
-    }
-    if (tile == T_256x32) return launch<256, 32, 4, 1, 2, VX_EPI_STORE>(p, stream);
-    if (tile == T_128x320) return launch<128, 320, 2, 4, 2, VX_EPI_STORE>(p, stream);
-    if (tile == T_256x256) return launch<256, 256, 4, 2, 2, VX_EPI_STORE>(p, stream);
-    if (tile == T_BIG) return launch<256, 320, 4, 2, 2, VX_EPI_STORE>(p, stream);
-    if (tile == T_SMALL64) return launch<64, 160, 1, 2, 3, VX_EPI_STORE>(p, stream);
-    if (tile == T_128x160) {
-      // pipeline depth of the 128 x 160 tile (VX_GEMM_STAGES128 = 2 | 3 | 4; A/B knob): the 16x16-level launches are
-      // DMA-latency bound at depth 2 (8192 x 1280 x 1280: 2 us per K-tile against 0.3 us of MFMA work)
-      static int st = -1;
-      if (st < 0) {
-        const char* e = getenv("VX_GEMM_STAGES128");
-        st = e ? atoi(e) : 2;
-      }
-      if (st == 3) return launch<128, 160, 2, 2, 3, VX_EPI_STORE>(p, stream);
-      if (st == 4) return launch<128, 160, 2, 2, 4, VX_EPI_STORE>(p, stream);
-      return launch<128, 160, 2, 2, 2, VX_EPI_STORE>(p, stream);
-    }
-    return launch<128, 128, 2, 2, 2, VX_EPI_STORE>(p, stream);
   } else if (p.epi == VX_EPI_GEGLU) {
     VX_REQUIRE(p.out != nullptr && (p.n % 32) == 0 && (p.ldc % 8) == 0,
                "vx_gemm: GEGLU needs n%%32==0 (value/gate rows interleaved in blocks of 8)");
-    if (vx_gemm_ring_eligible(p)) return vx_gemm_ring_launch(p, stream);
-    if (use_big(p)) return launch<256, 320, 4, 2, 2, VX_EPI_GEGLU>(p, stream);
-    return launch<128, 128, 2, 2, 2, VX_EPI_GEGLU>(p, stream);
   } else if (p.epi == VX_EPI_SPLIT) {
     VX_REQUIRE(p.n_parts >= 1 && p.n_parts <= 3 && p.part_cols > 0 && p.n == p.n_parts * p.part_cols,
                "vx_gemm: SPLIT n=%d != n_parts*part_cols", p.n);
@@ -1036,15 +1027,9 @@ static int vx_gemm_dispatch(const vx_gemm_params& p, hipStream_t stream) {
       else
         VX_REQUIRE((p.part_ld[i] % 8) == 0, "vx_gemm: part_ld%%8");
     }
-    if (p.a_fp8) {
-      if ((p.n % 320) == 0 && (long)ceil_div(p.m, 256) * (p.n / 320) >= 256)
-        return launch_impl<256, 320, 4, 2, 2, VX_EPI_SPLIT, true, true>(p, stream);
-      return launch_impl<128, 160, 2, 2, 2, VX_EPI_SPLIT, true, true>(p, stream);
-    }
-    if (use_big(p)) return launch<256, 320, 4, 2, 2, VX_EPI_SPLIT>(p, stream);
-    if (prefer160(p.n)) return launch<128, 160, 2, 2, 2, VX_EPI_SPLIT>(p, stream);
-    return launch<128, 128, 2, 2, 2, VX_EPI_SPLIT>(p, stream);
+  } else {
+    vx_set_error("vx_gemm: unknown epilogue %d", p.epi);
+    return VX_ERR_UNSUPPORTED;
   }
-  vx_set_error("vx_gemm: unknown epilogue %d", p.epi);
-  return VX_ERR_UNSUPPORTED;
+  return launch_plan(p, pl, stream);
 }

@@ -190,6 +190,10 @@ def _tile_key(p):
     return _lib.vx_gemm_config_name(C.byref(p)).decode()
 
 
+def _on_ring(p):
+    return _tile_key(p).startswith("gemm_ring")       # p will run on the persistent kernel (the one place that reads the name)
+
+
 def _launch_gemm(p, what):
     prof = GemmProfile.active
     if prof is None:
@@ -429,7 +433,7 @@ def _set_ln(p, ln, eps=1e-5):
     if stats.shape[1] == 4:
         # two-part sums: the persistent kernel finishes them in its epilogue; any other launch gets them finished first
         p.ln_stats_parts, p.ln_eps = 2, float(eps)
-        if p.k != 640 or not _lib.vx_gemm_config_name(C.byref(p)).decode().startswith("gemm_ring"):
+        if p.k != 640 or not _on_ring(p):
             # (5 such launches of ~5 us per DDIM step at 512x512 - profiles/r04y_trace_summary.txt: the V^T halves of the
             # 32x32-level QKV projections; every other consumer at that level runs on the persistent kernel - so the
             # finished statistics are not cached across consumers: each statistics version has ONE consumer of this kind)
@@ -565,19 +569,28 @@ def _ring_off(k):
     return RING_MODE[0] == 0 or (RING_MODE[0] == 1 and k > 1280)
 
 
+# The batch-independent ring rule is stated once, in `_item_tiles`: the persistent kernel's tile, and the tiles a nominal
+# CFG-pair launch (2 items) needs for the plain ring kernel / at least for its cooperative K split.  csrc/vx_gemm_ring.hip
+# holds the same numbers (R_BM, R_BN, the ring_hint == 0 threshold): sharing them needs an ABI entry, so they stay duplicated.
+RING_BM, RING_BN, RING_MIN_TILES, COOP_MIN_TILES = 256, 320, 192, 96
+
+
+def _item_tiles(m, n):
+    """(rows of ONE batch item, e.g. a 16-frame CFG half; 256 x 320 tiles of the nominal CFG-pair launch, 0 when an item or
+    n is not whole tiles) - never a function of how many items share the launch.  None outside frame_rows(..., items=)."""
+    items = _ITEMS[0]
+    if items is None or items <= 0 or m % items:
+        return None
+    rows = m // items
+    return rows, 0 if rows % RING_BM or n % RING_BN else (2 * rows // RING_BM) * (n // RING_BN)
+
+
 def _ring_hint(p):
-    """vx_gemm_params.ring_hint from batch-independent facts: rows of ONE batch item (a 16-frame CFG half) and N.
-    The ring kernel is chosen when a nominal CFG-pair launch (2 items) would have >= 192 tiles of 256 x 320 and an
-    item is a whole number of 256-row tiles; without the frame_rows context the library decides by the launch size."""
+    """vx_gemm_params.ring_hint: the ring kernel from RING_MIN_TILES `_item_tiles` on; outside frame_rows the library decides."""
     if _ring_off(p.k):
         return -1
-    items = _ITEMS[0]
-    if items is None or items <= 0 or p.m % items:
-        return 0
-    rows_item = p.m // items
-    if rows_item % 256 or p.n % 320:
-        return -1
-    return 1 if (2 * rows_item // 256) * (p.n // 320) >= 192 else -1
+    t = _item_tiles(p.m, p.n)
+    return 0 if t is None else 1 if t[1] >= RING_MIN_TILES else -1
 
 
 QK_RING = [os.environ.get("VX_QK_RING", "1") != "0"]
@@ -587,11 +600,8 @@ def qk_on_ring(m, c):
     """Whether the Q | K half of a fused, LayerNorm-folded QKV projection ([m, c] -> [m, 2c]) would run on the persistent
     ring kernel (same batch-independent rule as `_ring_hint`): then blocks._self_attention issues it there and leaves
     only V^T to the classic SPLIT epilogue."""
-    items = _ITEMS[0]
-    if not QK_RING[0] or items is None or items <= 0 or m % items or (2 * c) % 320 or c % 64:
-        return False
-    rows_item = m // items
-    return rows_item % 256 == 0 and (2 * rows_item // 256) * (2 * c // 320) >= 192 and not _ring_off(c)
+    t = _item_tiles(m, 2 * c)
+    return bool(QK_RING[0] and t and c % 64 == 0 and t[1] >= RING_MIN_TILES and not _ring_off(c))
 
 
 def _splitk(p, geom, device, plain):
@@ -638,18 +648,12 @@ def _coop_signature(p, rows_item):
 def ring_coop_applies(p):
     """Whether the launch p takes the cooperative split - a function of batch-independent facts only (rows of ONE item, N,
     K, the epilogue; never of how many items share the launch), so a CFG half computed alone sums in the same order.
-    Only where `_ring_hint` said "not the ring kernel" because a CFG pair has too few tiles: rows of an item a multiple of
-    256, 96 <= tiles of the nominal pair < 192, K >= COOP_MIN_K; the kernel's own limits are asked of the library."""
-    items = _ITEMS[0]
-    if items is None or items <= 0 or p.m % items or _ring_off(p.k):
+    Only where `_ring_hint` said "not the ring kernel" because a CFG pair has too few tiles: COOP_MIN_TILES <= `_item_tiles`
+    < RING_MIN_TILES, K >= COOP_MIN_K; the kernel's own limits are asked of the library."""
+    t = _item_tiles(p.m, p.n)
+    if t is None or _ring_off(p.k) or not COOP_MIN_TILES <= t[1] < RING_MIN_TILES:
         return False
-    rows_item = p.m // items
-    if rows_item % 256 or p.n % 320:
-        return False
-    tiles_pair = (2 * rows_item // 256) * (p.n // 320)
-    if not 96 <= tiles_pair < 192:
-        return False
-    sig = _coop_signature(p, rows_item)
+    sig = _coop_signature(p, t[0])
     lib_ok = _COOP_OK.get(sig)
     if lib_ok is None and RING_COOP[0] and p.k >= COOP_MIN_K[0]:
         lib_ok = _COOP_OK[sig] = bool(_lib.vx_gemm_ring_coop_ok(C.byref(p)))
@@ -657,7 +661,7 @@ def ring_coop_applies(p):
            "" if lib_ok else "the kernel's limits (epilogue / odd number of 64-channel chunks)")
     # logged once per deciding signature like the one-launch blocks' decisions (bench.py: block_paths)
     epi = ("+res" if p.residual else "") + ("+ln" if p.ln_stats else "") + ("+rowstats" if p.row_stats_out else "")
-    return _note_path("gemm_too_few_tiles", (("rows_item", rows_item), ("n", p.n), ("k", p.k), ("chunks", (p.c1 + p.c2) // 64),
+    return _note_path("gemm_too_few_tiles", (("rows_item", t[0]), ("n", p.n), ("k", p.k), ("chunks", (p.c1 + p.c2) // 64),
                                              ("epilogue", epi or "plain")), not why,
                       "persistent kernel, cooperative two-way K split" if not why else "128 x 160 tiles", why)
 
@@ -991,17 +995,16 @@ def gn_fold_applies(m, hw, c, n):
     the switch is on, the persistent 256 x 320 kernel takes the launch (decided from batch-independent facts, like
     `_ring_hint`), a 256-row tile never straddles a frame, and the per-frame weight copies (frames x n x c) are cheaper
     to write than the normalised tensor (2 x m x c): c = 320 in practice (the 64x64 and 96x96 levels)."""
-    items = _ITEMS[0]
+    t = _item_tiles(m, n)
     # (every deciding fact is in the key: the rows of ONE item included - ADVICE r05)
-    geom = (("c", c), ("n", n), ("hw", hw), ("rows_item", m // items if items and items > 0 and m % items == 0 else None))
+    geom = (("c", c), ("n", n), ("hw", hw), ("rows_item", t[0] if t else None))
     folded, applied = "GroupNorm folded into per-frame weights (no normalised tensor)", "GroupNorm apply pass + GEMM"
-    if not GN_FOLD[0] or items is None or items <= 0 or m % items or hw % 256 or n % 320 or c % 64:
+    if not GN_FOLD[0] or t is None or hw % RING_BM or n % RING_BN or c % 64:
         return _note_path("groupnorm_proj_in", geom, False, applied, "fold off or geometry not whole 256 x 320 tiles per frame")
     if _ring_off(c):
         # the persistent kernel is switched off (A/B knob ops.RING_MODE)
         return _note_path("groupnorm_proj_in", geom, False, applied, "persistent kernel switched off")
-    rows_item = m // items
-    ok = rows_item % 256 == 0 and (2 * rows_item // 256) * (n // 320) >= 192 and n * 2 <= hw
+    ok = t[1] >= RING_MIN_TILES and n * 2 <= hw
     return _note_path("groupnorm_proj_in", geom, ok, folded if ok else applied,
                       "" if ok else "per-frame weight copies would cost more than the normalised tensor")
 
