@@ -7,6 +7,7 @@ with a chosen sampler and step count (GPU box):
     python tools/sampler_bench.py --scheduler ddim --steps 25 --guidance-rescale 0.7 --guidance-end 0.6
     python tools/sampler_bench.py --scheduler ddim --steps 25 --init-video --strength 0.6 --mask lower-half
     python tools/sampler_bench.py --scheduler ddim --steps 25 --audio-guidance-scale 6 [--guidance-scale 1]
+    python tools/sampler_bench.py --scheduler ddim --steps 25 --apg-eta 0 --apg-norm-threshold 20 --apg-momentum -0.5
 Prints one JSON line: ms per clip (host clock around whole clips, ending in a device synchronise), the denoise and decode
 milliseconds of the same clips (HIP events), and the average microseconds of the per-step update launch (HIP events
 around each `ops.overlap_ddim_step` / `ops.overlap_multistep_step` / `ops.overlap_ancestral_step` of one further,
@@ -23,6 +24,10 @@ chunk (`postprocess`: which of the two ran), timed like the update launch.
 --audio-guidance-scale s_a (with --guidance-scale s, default 3.5) runs the rows of a separate audio scale (`rows`: three per
 window for s > 1, the rows (m, c) for s <= 1 < s_a); `combine3_us` / `rescale3_us` are then the `ops.combine_units3` /
 `ops.guidance_rescale3` launches of a guided step, timed like their two-row siblings.
+--apg-eta ETA [--apg-norm-threshold R] [--apg-momentum BETA] switches adaptive projected guidance on (with any of the row
+routes above; not with --guidance-rescale): `apg_us` is then the two launches of one `ops.guidance_apg` call, a guided
+step's, timed like the update launch, and `apg_combine_us` the plain combine of the same rows (`ops.combine_units` /
+`ops.combine_units3` into a scratch buffer, right after every APG call of the same instrumented clip), for comparison.
 --frames F --context-frames f --context-overlap o --context-schedule uniform|uniform_fit choose the clip length and its
 windows (defaults: 16 frames in one window of 16, overlap 4, `uniform`); --overlap-blend mean|linear|pyramid the stitch of
 overlapping windows - a weighted blend adds one `ops.overlap_blend` launch per step (`overlap_blend_us`, timed like the
@@ -50,6 +55,10 @@ def main():
     ap.add_argument("--guidance-scale", type=float, default=3.5)
     ap.add_argument("--audio-guidance-scale", type=float, default=None,
                     help="a separate scale for the audio (three rows per window for --guidance-scale > 1)")
+    ap.add_argument("--apg-eta", type=float, default=None,
+                    help="adaptive projected guidance: the scale of the part parallel to the conditional prediction")
+    ap.add_argument("--apg-norm-threshold", type=float, default=0.0, help="cap of a guidance difference's norm per frame")
+    ap.add_argument("--apg-momentum", type=float, default=0.0)
     ap.add_argument("--init-video", action="store_true", help="start from a synthetic init video (img2img)")
     ap.add_argument("--strength", type=float, default=1.0, help="run the last int(steps * strength) timesteps")
     ap.add_argument("--mask", choices=("none", "lower-half"), default="none",
@@ -133,6 +142,8 @@ def main():
         extra["audio_guidance_scale"] = args.audio_guidance_scale
     if args.overlap_blend != "mean":
         extra["overlap_blend"] = args.overlap_blend
+    if args.apg_eta is not None:
+        extra["apg"] = (args.apg_eta, args.apg_norm_threshold, args.apg_momentum)
 
     def one_clip(ev=None):
         if ev:
@@ -187,6 +198,34 @@ def main():
             setattr(ops, name, orig)
         torch.cuda.synchronize()
         return len(marks), 1e3 * sum(s.elapsed_time(e) for s, e in marks) / max(len(marks), 1)
+
+    def apg_launch_us():
+        """(the ops.guidance_apg call, the plain combine of the same rows) of a guided step, microseconds: one instrumented
+        clip in which every APG call is followed by the combine into a scratch buffer."""
+        orig, marks = ops.guidance_apg, []
+
+        def timed(fn):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            fn()
+            e.record()
+            return s, e
+
+        def marked(gathered, uidx, c, f, hw, guidance, audio_guidance, *rest):
+            a = timed(lambda: orig(gathered, uidx, c, f, hw, guidance, audio_guidance, *rest))
+            scratch = torch.empty_like(rest[-1])
+            if uidx.shape[1] == 3:
+                b = timed(lambda: ops.combine_units3(gathered, uidx, c, f, hw, guidance, audio_guidance, scratch))
+            else:
+                b = timed(lambda: ops.combine_units(gathered, uidx, c, f, hw, guidance, scratch))
+            marks.append((a, b))
+        ops.guidance_apg = marked
+        try:
+            one_clip()
+        finally:
+            ops.guidance_apg = orig
+        torch.cuda.synchronize()
+        return [1e3 * sum(m[i][0].elapsed_time(m[i][1]) for m in marks) / max(len(marks), 1) for i in (0, 1)]
     n_updates, update_us = update_launch_us(update)
     blend_launches, blend_us = update_launch_us("known_blend") if args.init_video else (0, None)
     wblend_launches, wblend_us = update_launch_us("overlap_blend") if args.overlap_blend != "mean" else (0, None)
@@ -198,9 +237,12 @@ def main():
     rescaled = args.guidance_rescale > 0 and guided
     rescale_us = round(update_launch_us("guidance_rescale")[1], 2) if rescaled and not three else None
     rescale3_us = round(update_launch_us("guidance_rescale3")[1], 2) if rescaled and three else None
-    combine3_us = round(update_launch_us("combine_units3")[1], 2) if three and guided and not rescaled else None
+    combine3_us = round(update_launch_us("combine_units3")[1], 2) if three and guided and not rescaled and args.apg_eta is None else None
+    apg_us = apg_combine_us = None
+    if args.apg_eta is not None and guided:
+        apg_us, apg_combine_us = (round(v, 2) for v in apg_launch_us())
     combine_us = None
-    if (rescale_us is None and rescale3_us is None and combine3_us is None) or guided < args.steps:
+    if (rescale_us is None and rescale3_us is None and combine3_us is None and apg_us is None) or guided < args.steps:
         combine_us = round(update_launch_us("combine_units")[1], 2)
     ddim_us = None
     if update == "overlap_ancestral_step":
@@ -223,6 +265,7 @@ def main():
         ddim_update_us=ddim_us, guidance_rescale=args.guidance_rescale, guidance_start=args.guidance_start,
         guidance_end=args.guidance_end, guided_steps=guided, rescale_us=rescale_us, combine_us=combine_us,
         audio_guidance_scale=args.audio_guidance_scale, rows=rows, combine3_us=combine3_us, rescale3_us=rescale3_us,
+        apg=pipe.last_guidance.get("apg"), apg_us=apg_us, apg_combine_us=apg_combine_us,
         clip_ms_min=round(min(per_clip), 2), clip_ms_max=round(max(per_clip), 2), init_video=args.init_video,
         strength=args.strength, mask=args.mask, begin_index=begin, steps_run=len(timesteps), encode_ms=encode_ms,
         blend_launches=blend_launches, blend_us=None if blend_us is None else round(blend_us, 2), postprocess=post,

@@ -1,5 +1,6 @@
 """Reader of the C ABI header include/vexpress_hip.h: the ABI version, the enum constants, the parameter structs and the
 prototypes, as ctypes types.  lib.py binds both libraries from it, so the header is the only statement of the contract.
+include/vexpress_hip_guidance.h, the second header (entry points added without touching the first), is read the same way.
 Pure Python: no torch, no shared library.  It fails closed: once comments, preprocessor lines, the extern "C" braces and
 every declaration it has understood are taken out, anything but whitespace left over is an ImportError naming it."""
 import collections
@@ -9,6 +10,7 @@ import os
 import re
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "vexpress_hip.h")
+GUIDANCE_HEADER = os.path.join(os.path.dirname(HEADER), "vexpress_hip_guidance.h")
 
 # version: int; enums: {name: value}; structs: {C name: [(field, ctypes type, array length or 0)]}; classes: {C name: the
 # ctypes.Structure built from those fields}; functions: {name: (restype, [(parameter, ctypes type)])}, all in header order
@@ -35,8 +37,9 @@ def _ctype(m, classes, where):
     raise ImportError(f"{where}: no ctypes type for {' '.join(m.group(0).split())!r}")
 
 
-def parse(text, where=HEADER):
-    """The Abi that the header `text` declares; ImportError (naming the text) for anything it does not understand."""
+def parse(text, where=HEADER, macro="VX_ABI_VERSION"):
+    """The Abi that the header `text` declares, its version the value of `macro`; ImportError (naming the text) for
+    anything it does not understand."""
     abi = Abi(None, {}, {}, {}, {})
 
     def bad(what, s):
@@ -80,9 +83,9 @@ def parse(text, where=HEADER):
         return ""
 
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
-    version = re.search(r"^[ \t]*#[ \t]*define[ \t]+VX_ABI_VERSION[ \t]+(\d+)[ \t]*$", text, flags=re.M)
+    version = re.search(r"^[ \t]*#[ \t]*define[ \t]+" + re.escape(macro) + r"[ \t]+(\d+)[ \t]*$", text, flags=re.M)
     if not version:
-        raise ImportError(f"{where}: no `#define VX_ABI_VERSION <number>`")
+        raise ImportError(f"{where}: no `#define {macro} <number>`")
     text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
     text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, count=1, flags=re.S)
     for pattern, reader in ((_ENUM, enum), (_STRUCT, struct), (_PROTO, proto)):     # structs before the prototypes that point to them
@@ -97,3 +100,10 @@ def header():
     """include/vexpress_hip.h, parsed once per process."""
     with open(HEADER) as f:
         return parse(f.read())
+
+
+@functools.lru_cache(maxsize=None)
+def guidance_header():
+    """include/vexpress_hip_guidance.h, parsed once per process (version macro VX_GUIDANCE_ABI_VERSION)."""
+    with open(GUIDANCE_HEADER) as f:
+        return parse(f.read(), GUIDANCE_HEADER, "VX_GUIDANCE_ABI_VERSION")

@@ -1,4 +1,4 @@
-"""Tensor-level wrappers around the C ABI (include/vexpress_hip.h).
+"""Tensor-level wrappers around the C ABI (include/vexpress_hip.h, include/vexpress_hip_guidance.h).
 
 PyTorch is used for device memory and streams only: every wrapper passes raw device pointers, explicit
 shapes/strides and `torch.cuda.current_stream()` to libvexpress_hip.so.  Activations are bf16
@@ -6,6 +6,7 @@ channels-last tokens `[frames, H*W, C]`; weights are pre-laid-out by `weights.py
 """
 import ctypes as C
 import logging
+import math
 import os
 
 import torch
@@ -1397,6 +1398,49 @@ def guidance_rescale3(gathered, unit_index, c, f, hw, guidance, audio_guidance, 
     L.check(_lib.vx_guidance_rescale3(_ptr(gathered), _ptr(unit_index), nW, S, c, f, hw, float(guidance),
                                       float(audio_guidance), float(phi), _ptr(workspace), workspace.numel(),
                                       _ptr(preds), _stream()), "vx_guidance_rescale3")
+
+
+def guidance_apg_ws_floats(nW, rows, f, hw):
+    """float32 elements of the workspace `guidance_apg` needs for nW windows of `rows` rows, f frames of hw pixels."""
+    return int(_lib.vx_guidance_apg_ws_floats(int(nW), int(rows), int(f), int(hw)))
+
+
+def guidance_apg(gathered, unit_index, c, f, hw, guidance, audio_guidance, eta, norm_threshold, momentum, momentum_buf,
+                 workspace, preds):
+    """Adaptive projected guidance on the model output (vx_guidance_apg, include/vexpress_hip_guidance.h): gathered fp32
+    [units_total, (f/S)*hw, c]; unit_index int32 [nW, rows, S], rows = 2 ((u, c) or (m, c), guided by `guidance`) or 3
+    ((u, m, c): `guidance` on m - u, `audio_guidance` on c - m) -> preds fp32 [nW, c, f, hw].  Per frame of a window each
+    difference d runs through the momentum (dbar = d + momentum * previous dbar, kept in momentum_buf fp32
+    [rows - 1, nW, c, f, hw]: None if and only if momentum == 0), is capped at the norm `norm_threshold` (0: no cap) and
+    has its part parallel to the conditional row damped by `eta` (1 keeps it, 0 removes it).  workspace: float32, at
+    least guidance_apg_ws_floats(nW, rows, f, hw) elements."""
+    rows = unit_index.shape[1] if unit_index.dim() == 3 else 0
+    if rows not in (2, 3):
+        raise ValueError("guidance_apg: unit_index must be [nW, 2, S] (the rows (u, c) or (m, c)) or [nW, 3, S] "
+                         "(the rows u, m, c of every window)")
+    nW, S = _check_units("guidance_apg", rows, gathered, unit_index, c, f, hw, preds)
+    eta, r, beta = float(eta), float(norm_threshold), float(momentum)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"guidance_apg: eta must lie in [0, 1], got {eta}")
+    if not (math.isfinite(r) and r >= 0.0):
+        raise ValueError(f"guidance_apg: norm_threshold must be a finite number >= 0, got {norm_threshold}")
+    if not abs(beta) < 1.0:
+        raise ValueError(f"guidance_apg: momentum must satisfy |momentum| < 1, got {momentum}")
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise TypeError("guidance_apg: contiguous float32 workspace expected")
+    if workspace.numel() < guidance_apg_ws_floats(nW, rows, f, hw):
+        raise ValueError("guidance_apg: workspace smaller than guidance_apg_ws_floats(nW, rows, f, hw)")
+    if (beta != 0.0) != (momentum_buf is not None):
+        raise ValueError("guidance_apg: momentum_buf must be given when momentum != 0 and None when momentum == 0")
+    if momentum_buf is not None:
+        if momentum_buf.dtype != torch.float32 or not momentum_buf.is_contiguous():
+            raise TypeError("guidance_apg: contiguous float32 momentum_buf expected")
+        if momentum_buf.numel() != (rows - 1) * preds.numel():
+            raise ValueError("guidance_apg: momentum_buf must hold [rows - 1, nW, c, f, hw] elements")
+    L.check(_lib.vx_guidance_apg(_ptr(gathered), _ptr(unit_index), nW, rows, S, c, f, hw, float(guidance),
+                                 float(audio_guidance), eta, r, beta,
+                                 _ptr(momentum_buf), _ptr(workspace),
+                                 workspace.numel(), _ptr(preds), _stream()), "vx_guidance_apg")
 
 
 def overlap_ddim_step(latents, preds, terms, frame_ids, counts, coef):

@@ -75,6 +75,24 @@ def check_guidance(guidance_rescale, guidance_start, guidance_end, n):
     return phi, guided_steps(n, start, end)
 
 
+def check_apg(apg, guidance_rescale=0.0):
+    """Validates the adaptive-projected-guidance controls `apg` = None (off) or (eta, norm_threshold, momentum); returns
+    None or the three as floats."""
+    if apg is None or apg[0] is None:
+        return None
+    eta, r, beta = (float(v) for v in apg)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"apg_eta must lie in [0, 1], got {apg[0]}")
+    if not (math.isfinite(r) and r >= 0.0):
+        raise ValueError(f"apg_norm_threshold must be a finite number >= 0 (0: no cap), got {apg[1]}")
+    if not abs(beta) < 1.0:
+        raise ValueError(f"apg_momentum must satisfy |apg_momentum| < 1, got {apg[2]}")
+    if float(guidance_rescale) > 0.0:
+        raise ValueError("apg_eta together with guidance_rescale > 0: both fight the same defect (the over-driven guided "
+                         "prediction), and the combination is not built; pass one of them")
+    return eta, r, beta
+
+
 def check_audio_guidance(audio_guidance_scale):
     """Validates `audio_guidance_scale`; returns it as a float, or None."""
     if audio_guidance_scale is None:
@@ -170,7 +188,8 @@ class VExpressPipeline:
         # the guidance controls of the last denoise() call: dict(guided_steps, steps, rescale, unguided_schedule), the
         # last one the last_schedule-style dict of the conditional-only plan of its unguided steps, or None.  A call that
         # passes audio_guidance_scale also finds `rows` (guidance_rows: ("u", "c"), ("u", "m", "c"), ("m", "c") or
-        # ("c",)) and `audio_scale` in it; without the keyword the dict is what it was before the keyword existed
+        # ("c",)) and `audio_scale` in it; without the keyword the dict is what it was before the keyword existed.  A call
+        # that passes apg (apg_eta) finds `apg` = dict(eta, norm_threshold, momentum), or None where it was ignored
         self.last_guidance = {}
         # init-video sampling of the last denoise() call: dict(begin_index, masked, blend_launches) - the step index the
         # loop started at, whether a latent mask was blended in after every step, and the vx_known_blend launches of the
@@ -421,7 +440,8 @@ class VExpressPipeline:
     @_in_unet_element_type
     def denoise(self, latents, kps_tokens, audio, timesteps, windows, guidance_scale, callback=None,
                 callback_steps=1, *, begin_index=None, eta=0.0, noise_seed=None, guidance_rescale=0.0,
-                guidance_start=0.0, guidance_end=1.0, known=None, audio_guidance_scale=None, overlap_blend="mean"):
+                guidance_start=0.0, guidance_end=1.0, known=None, audio_guidance_scale=None, overlap_blend="mean",
+                apg=None):
         """pipelines/v_express_pipeline.py:526-583.  latents fp32 [1,4,F,h,w] (device, updated in place);
         kps_tokens bf16 [b, F, hw, C0]; audio bf16 [b, F, n_ctx, 768] with b = 2 (uncond, cond) under classifier-free
         guidance (guidance_scale > 1, :443) and b = 1 (the conditional row only) without.
@@ -439,6 +459,12 @@ class VExpressPipeline:
         and drops the audio; the rows a guided step runs are guidance_rows(s, s_a) - three per window for s > 1 and
         s_a != s (vx_combine_units3 / vx_guidance_rescale3), (m, c) with guidance s_a for s <= 1 < s_a; both need the
         b = 2 conditioning.  The rescale is towards std(c); an unguided step runs c alone, and neither scale applies.
+        Adaptive projected guidance: apg = (eta, norm_threshold, momentum) (None: off) replaces the combine of a guided
+        step by vx_guidance_apg - per window and per frame, each guidance difference (c - u; m - u and c - m with three
+        rows; c - m for the rows (m, c)) runs through a momentum buffer the loop owns (zeros before the first guided
+        step), is capped at the norm norm_threshold (0: no cap) and has its part parallel to the conditional prediction
+        scaled by eta (Sadat et al., diffusers' AdaptiveProjectedGuidance, on the model output).  Not together with
+        guidance_rescale; an unguided step neither reads nor advances the buffers; ignored without guidance.
         Init-video sampling (every sampler): known = (init, noise, m) - the clip's clean latents and the N(0,1) tensor,
         fp32 shaped like `latents`, and the latent mask fp32 [F, h*w] in [0, 1] (1 = regenerate, 0 = keep) or None.  The
         loop then starts from a_b init + s_b noise, b = begin_index (what `latents` held is not read), with (a_j, s_j)
@@ -459,6 +485,7 @@ class VExpressPipeline:
         raw_weights = None if blend_kind == "mean" else blend_weights(windows, overlap_blend)
         guidance_rescale, guided = check_guidance(guidance_rescale, guidance_start, guidance_end, len(timesteps))
         row_names = guidance_rows(guidance_scale, audio_guidance_scale)
+        apg = check_apg(apg, guidance_rescale)
         init, noise, kmask = check_known(known, latents)
         if kind != "ddim" or known is not None:
             all_ts = [int(t) for t in self.scheduler.timesteps.tolist()]
@@ -485,7 +512,7 @@ class VExpressPipeline:
         guidance = Guidance(row_names, guidance_scale, audio_guidance_scale, guidance_rescale, guided, kps_tokens, audio,
                             lambda audio_is_zero, half_rows: self._unit_plan(latents, kps_tokens, audio, audio_is_zero,
                                                                              windows, win_ids, half_rows),
-                            nW, C, f, hw, dev)
+                            nW, C, f, hw, dev, apg=apg)
         self.last_schedule, self.last_guidance = guidance.schedule, guidance.report
         preds = torch.empty((nW, C, f, hw), device=dev, dtype=torch.float32)
         sampler = Sampler(self.scheduler, kind, latents, timesteps, begin_index, eta, noise_seed)
@@ -555,6 +582,7 @@ class VExpressPipeline:
                  noise_seed: Optional[int] = None, output_device="cpu", decode=True, guidance_rescale: float = 0.0,
                  guidance_start: float = 0.0, guidance_end: float = 1.0, init_video=None, init_latents=None,
                  mask=None, composite=True, audio_guidance_scale: Optional[float] = None, overlap_blend="mean",
+                 apg_eta: Optional[float] = None, apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0,
                  **kwargs):
         """Window stitch: `context_schedule` = "uniform" (the reference's; a clip length that is not f + k (f - o) ends in
         a reflected window with duplicate frames) or "uniform_fit" (the same number of windows spread evenly over any
@@ -565,6 +593,12 @@ class VExpressPipeline:
         guides on the audio apart from the reference image and the keypoints: u + s (m - u) + s_a (c - m), m the
         prediction with bank and keypoints but silent audio (three rows per window for s > 1 and s_a != s; the rows
         (m, c) for s <= 1 < s_a).  The prologue runs in the CFG layout whenever either scale exceeds 1.
+        Adaptive projected guidance: `apg_eta` in [0, 1] (default None: off) switches it on for the guided steps - the
+        part of each guidance difference parallel to the conditional prediction is scaled by apg_eta (0 removes it, the
+        published remedy for the saturation of a large scale), the difference is capped at the norm
+        `apg_norm_threshold` per frame (0: no cap) and averaged with `apg_momentum` (|.| < 1, usually negative) over the
+        guided steps.  It acts on the model output per window and frame, with every row route and sampler; it cannot be
+        combined with `guidance_rescale`, and without guidance it is ignored.
         Init-video sampling (diffusers' img2img / inpaint semantics for a 4-channel UNet): `init_video` fp32
         [1, 3, F, H, W] in [0, 1] (VAE-encoded here; needs v_express_amd.AutoencoderKL) or `init_latents`
         [1, 4, F, h, w] (clean, already scaled) makes the loop start from the clip noised to the level of `strength`
@@ -578,6 +612,7 @@ class VExpressPipeline:
         ancestral = kind in ANCESTRAL
         check_guidance(guidance_rescale, guidance_start, guidance_end, max(int(num_inference_steps), 1))
         audio_guidance_scale = check_audio_guidance(audio_guidance_scale)
+        apg = check_apg((apg_eta, apg_norm_threshold, apg_momentum), guidance_rescale)
 
         def clip_windows():
             return list(get_context_scheduler(context_schedule)(
@@ -674,7 +709,7 @@ class VExpressPipeline:
         self.denoise(lat, kps_tokens, audio, timesteps, windows, guidance_scale, callback, callback_steps or 1,
                      begin_index=begin_index, eta=eta, noise_seed=noise_seed, guidance_rescale=guidance_rescale,
                      guidance_start=guidance_start, guidance_end=guidance_end, known=known,
-                     audio_guidance_scale=audio_guidance_scale, overlap_blend=overlap_blend)
+                     audio_guidance_scale=audio_guidance_scale, overlap_blend=overlap_blend, apg=apg)
         self.last_overlap["schedule"] = context_schedule
         if timed:
             ev[1].record()

@@ -89,12 +89,14 @@ class Stitch:
 class Guidance:
     """The rows of a guided step (`row_names`: guidance_rows), the plan of the guided steps and - only when some step runs
     without guidance - the plan of the conditional row alone, and the one launch that turns a step's gathered units into
-    window predictions: vx_combine_units, vx_combine_units3, vx_guidance_rescale or vx_guidance_rescale3.
+    window predictions: vx_combine_units, vx_combine_units3, vx_guidance_rescale, vx_guidance_rescale3 or - with
+    `apg` = (eta, norm_threshold, momentum) - vx_guidance_apg, whose workspace and zero-initialised momentum buffers
+    (`momentum`: one per guidance difference, advanced by the guided steps only) live here.
     `unit_plan(half_rows)` builds a plan (VExpressPipeline._unit_plan, given the all-zero audio rows): collective, so both
     plans are built here, on every rank, before the loop.  `report` is last_guidance, `schedule` last_schedule."""
 
     def __init__(self, row_names, guidance_scale, audio_guidance_scale, rescale, guided, kps_tokens, audio, unit_plan,
-                 nW, C, f, hw, dev):
+                 nW, C, f, hw, dev, apg=None):
         steps = len(guided)
         do_cfg = len(row_names) > 1                   # a guided step combines rows
         cond_rows = 2 if do_cfg else 1
@@ -119,9 +121,17 @@ class Guidance:
             self.report.update(rows=row_names, audio_scale=float(audio_guidance_scale))
         # the one scale of a two-row combine: (m, c) is guided by the audio scale; one row: u + 1 (u - u)
         scale2 = (float(audio_guidance_scale) if row_names == ("m", "c") else guidance_scale) if do_cfg else 1.0
-        ws = None
+        if apg is not None:                           # (like the rescale: nothing to project without guidance)
+            self.report.update(apg=dict(zip(("eta", "norm_threshold", "momentum"), apg)) if do_cfg else None)
+            apg = apg if do_cfg and any(guided) else None
+        ws = self.momentum = None
         if rescale > 0.0 and any(guided):
             ws = torch.empty(ops.guidance_rescale_ws_floats(nW, f, hw), device=dev, dtype=torch.float32)
+        if apg is not None:
+            eta, r, beta = apg
+            ws = torch.empty(ops.guidance_apg_ws_floats(nW, len(row_names), f, hw), device=dev, dtype=torch.float32)
+            if beta != 0.0:
+                self.momentum = torch.zeros((len(row_names) - 1, nW, C, f, hw), device=dev, dtype=torch.float32)
         geo, s, s_a, self.workspace = (C, f, hw), guidance_scale, audio_guidance_scale, ws
 
         # the launch of a guided step - u + s (m - u) + s_a (c - m) or the CFG combine (:548-550), each window rescaled
@@ -131,7 +141,12 @@ class Guidance:
         def rescale2(g, u, p): ops.guidance_rescale(g, u, *geo, scale2, rescale, ws, p)
         def combine2(g, u, p): ops.combine_units(g, u, *geo, scale2, p)
         def conditional(g, u, p): ops.combine_units(g, u, *geo, 1.0, p)
-        if len(row_names) == 3:
+        # adaptive projected guidance: every difference of the rows projected on c, capped and run through its momentum
+        def apg3(g, u, p): ops.guidance_apg(g, u, *geo, s, s_a, eta, r, beta, self.momentum, ws, p)
+        def apg2(g, u, p): ops.guidance_apg(g, u, *geo, scale2, 0.0, eta, r, beta, self.momentum, ws, p)
+        if apg is not None:
+            guided_op = apg3 if len(row_names) == 3 else apg2
+        elif len(row_names) == 3:
             guided_op = combine3 if ws is None else rescale3
         else:
             guided_op = combine2 if ws is None else rescale2
