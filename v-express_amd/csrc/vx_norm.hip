@@ -11,6 +11,13 @@
 //                 scale/shift in LDS and streams its slice: y = x*scale + shift (+SiLU), 16-B loads/stores.
 // Algorithmic traffic: stats read 2 B/elem, apply read 2 + write 2 B/elem (the second read mostly hits the
 // 256 MB infinity cache for UNet-sized tensors).
+// LDS limits, checked on the host before anything is launched: gn_stats takes pixel lanes x C x 2 floats (<= 64 KB); gn_apply
+// and gn_fold_linear take 2 C + 2 groups floats + GN_SUBS x groups x 2 doubles.  With one channel per group that is 144 B per
+// channel - 73,728 B at the wav2vec2 feature encoder's C = groups = 512.  gn_apply accepts up to GN_APPLY_LDS_MAX = 160 KB, all a
+// gfx950 workgroup can have (C = groups <= 1136), and refuses more with VX_ERR_INVALID; gn_fold_linear keeps its 64 KB limit
+// (it only runs in front of 320 / 640-channel projections).  Above 64 KB gn_apply also raises its dynamic-LDS attribute first.
+// That is for consistency with the other kernels here that ask for more; whether the runtime needs it is not established
+// (the wav2vec2 feature encoder made the same 73,728-B launch before the attribute was raised here).
 //
 // LayerNorm: one wave per row, the whole row lives in registers (C <= 64*8*MAXC), two-pass mean/variance via
 // wave shuffles, fused affine and the motion module's additive sinusoid table.
@@ -29,6 +36,7 @@ constexpr int GN_MAX_SETS = 2;   // chunks per thread per pixel -> C <= 8*256*2 
 // loads per thread in flight.
 constexpr int GN_UNROLL = 4;
 constexpr int GN_SUBS = 8;      // parallel sub-sums of the per-slice partials in gn_apply
+constexpr size_t GN_APPLY_LDS_MAX = 160 * 1024;   // the LDS of one gfx950 CU: the most one workgroup can be given
 
 struct GnPlan {
   const bf16_t* base[GN_MAX_SETS];   // first pixel of the frame, at this thread's chunk (nullptr: no chunk)
@@ -589,6 +597,26 @@ __global__ __launch_bounds__(256) void layernorm_fp8_kernel(const bf16_t* __rest
   }
 }
 
+// gn_apply_kernel's dynamic LDS: scale[C] + shift[C] + gstat[2*groups] floats, then the fp64 sub-sums (8-byte aligned: C, groups even)
+inline size_t gn_apply_lds(int C, int groups) {
+  return (size_t)(2 * C + 2 * groups) * sizeof(float) + (size_t)GN_SUBS * groups * 2 * sizeof(double);
+}
+
+// Above 64 KB the kernel's dynamic-LDS attribute is raised first (once per new maximum).  `granted` is one unsynchronised value per
+// process, like the `attr_set` flags of the other launchers: a second device in the same process does not get the attribute set,
+// and two host threads may both set it (setting it twice is harmless).
+int gn_apply_reserve_lds(size_t smem) {
+  static size_t granted = 64 * 1024;
+  if (smem <= granted) return 0;
+  hipError_t e = hipFuncSetAttribute((const void*)gn_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  if (e != hipSuccess) {
+    vx_set_error("vx_groupnorm: hipFuncSetAttribute(%zu B LDS) failed: %s", smem, hipGetErrorString(e));
+    return VX_ERR_HIP;
+  }
+  granted = smem;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int64_t vx_groupnorm_ws_floats(int frames, int slices, int groups) {
@@ -619,13 +647,14 @@ extern "C" int vx_groupnorm(const void* x1, int c1, const void* x2, int c2, int 
   const int tp = nchunks < GN_THREADS ? nchunks : GN_THREADS;
   const int pl_count = GN_THREADS / tp;
   size_t smem_stats = (size_t)pl_count * C * 2 * sizeof(float);
-  // scale[C] + shift[C] + gstat[2*groups] floats, then the fp64 sub-sums (8-byte aligned: C, groups even)
-  size_t smem_apply = (size_t)(2 * C + 2 * groups) * sizeof(float) + (size_t)GN_SUBS * groups * 2 * sizeof(double);
+  const size_t smem_apply = gn_apply_lds(C, groups);
   VX_REQUIRE(smem_stats <= 64 * 1024, "vx_groupnorm: stats LDS %zu too large", smem_stats);
+  VX_REQUIRE(smem_apply <= GN_APPLY_LDS_MAX, "vx_groupnorm: apply LDS %zu B (C=%d, groups=%d) exceeds %zu", smem_apply, C,
+             groups, GN_APPLY_LDS_MAX);
+  if (int rc = gn_apply_reserve_lds(smem_apply)) return rc;
   hipLaunchKernelGGL(gn_stats_kernel, dim3(frames * slices), dim3(GN_THREADS), smem_stats, stream,
                      (const bf16_t*)x1, c1, (const bf16_t*)x2, c2, hw, groups, slices, slice_pix, ws);
-  int rc = vx_check_launch("vx_groupnorm(stats)");
-  if (rc) return rc;
+  if (int rc = vx_check_launch("vx_groupnorm(stats)")) return rc;
   // The apply pass may cut a frame into fewer, larger pieces than the statistics pass: every block re-reduces the
   // frame's partial sums before it streams (a fixed ~2 us prologue), so 64 blocks of 64 pixels per frame pay it 64 times.
   // VX_GN_APPLY_SLICES (A/B knob): upper bound on the apply pass's pieces per frame; element-wise pass, same bits.
@@ -662,7 +691,10 @@ extern "C" int vx_groupnorm_apply(const void* x1, int c1, const void* x2, int c2
   int w_shift = -1;
   for (int sft = 0; sft < 31; ++sft)
     if ((1 << sft) == width) w_shift = sft;
-  const size_t smem_apply = (size_t)(2 * C + 2 * groups) * sizeof(float) + (size_t)GN_SUBS * groups * 2 * sizeof(double);
+  const size_t smem_apply = gn_apply_lds(C, groups);
+  VX_REQUIRE(smem_apply <= GN_APPLY_LDS_MAX, "vx_groupnorm_apply: apply LDS %zu B (C=%d, groups=%d) exceeds %zu", smem_apply,
+             C, groups, GN_APPLY_LDS_MAX);
+  if (int rc = gn_apply_reserve_lds(smem_apply)) return rc;
   const int apix = ceil_div(hw, slices);
   hipLaunchKernelGGL(gn_apply_kernel, dim3(frames * slices), dim3(GN_THREADS), smem_apply, stream, (const bf16_t*)x1, c1,
                      (const bf16_t*)x2, c2, hw, groups, eps, gamma, beta, silu, (bf16_t*)out, slices, apix, ws, width,
