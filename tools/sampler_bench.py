@@ -3,6 +3,7 @@ with a chosen sampler and step count (GPU box):
     python tools/sampler_bench.py --scheduler ddim --steps 25
     python tools/sampler_bench.py --scheduler dpm --steps 15 [--order 2]
     python tools/sampler_bench.py --scheduler euler-a --steps 25
+    python tools/sampler_bench.py --scheduler euler|lms|pndm --steps 25 [--lms-order 4]
     python tools/sampler_bench.py --scheduler ddim-eta --eta 1.0 --steps 25
     python tools/sampler_bench.py --scheduler ddim --steps 25 --guidance-rescale 0.7 --guidance-end 0.6
     python tools/sampler_bench.py --scheduler ddim --steps 25 --init-video --strength 0.6 --mask lower-half
@@ -10,8 +11,8 @@ with a chosen sampler and step count (GPU box):
     python tools/sampler_bench.py --scheduler ddim --steps 25 --apg-eta 0 --apg-norm-threshold 20 --apg-momentum -0.5
 Prints one JSON line: ms per clip (host clock around whole clips, ending in a device synchronise), the denoise and decode
 milliseconds of the same clips (HIP events), and the average microseconds of the per-step update launch (HIP events
-around each `ops.overlap_ddim_step` / `ops.overlap_multistep_step` / `ops.overlap_ancestral_step` of one further,
-instrumented clip; for the ancestral samplers also `ddim_update_us`, the DDIM update of the same clip timed the same way,
+around each `ops.overlap_ddim_step` / `ops.overlap_multistep_step` / `ops.overlap_ancestral_step` /
+`ops.overlap_linear_step` (Euler, LMS, PNDM - whose list has steps + 1 entries) of one further, instrumented clip; for the ancestral samplers also `ddim_update_us`, the DDIM update of the same clip timed the same way,
 for comparison).  The guidance controls (--guidance-rescale, --guidance-start, --guidance-end) are passed to the loop; the
 line then also carries them, the number of guided steps, `rescale_us` (the `ops.guidance_rescale` launches of a step,
 timed the same way; it stands in for the one `vx_combine_units` launch of a step without the rescale, `combine_us`) and
@@ -45,10 +46,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scheduler", choices=("ddim", "dpm", "ddim-eta", "euler-a"), default="ddim")
+    ap.add_argument("--scheduler", choices=("ddim", "dpm", "ddim-eta", "euler-a", "euler", "lms", "pndm"),
+                    default="ddim")
     ap.add_argument("--eta", type=float, default=1.0, help="DDIM eta of --scheduler ddim-eta")
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--order", type=int, choices=(1, 2), default=2, help="DPM-Solver++ solver_order")
+    ap.add_argument("--lms-order", type=int, choices=(1, 2, 3, 4), default=4, help="LMSDiscreteScheduler lms_order")
     ap.add_argument("--guidance-rescale", type=float, default=0.0, help="phi of the CFG rescale")
     ap.add_argument("--guidance-start", type=float, default=0.0)
     ap.add_argument("--guidance-end", type=float, default=1.0)
@@ -107,6 +110,12 @@ def main():
         update = "overlap_ddim_step" if args.scheduler == "ddim" else "overlap_ancestral_step"
     elif args.scheduler == "euler-a":
         sched, update = vx.EulerAncestralDiscreteScheduler(**kw), "overlap_ancestral_step"
+    elif args.scheduler == "euler":
+        sched, update = vx.EulerDiscreteScheduler(**kw), "overlap_linear_step"
+    elif args.scheduler == "lms":
+        sched, update = vx.LMSDiscreteScheduler(**kw, lms_order=args.lms_order), "overlap_linear_step"
+    elif args.scheduler == "pndm":
+        sched, update = vx.PNDMScheduler(**kw, skip_prk_steps=True), "overlap_linear_step"
     else:
         sched, update = vx.DPMSolverMultistepScheduler(**kw, solver_order=args.order), "overlap_multistep_step"
     pipe = vx.VExpressPipeline(vae=vae, reference_net=refnet, denoising_unet=unet, scheduler=sched)
@@ -118,6 +127,8 @@ def main():
     reader.update(writer, True)
     sched.set_timesteps(args.steps)
     begin = max(args.steps - min(int(args.steps * args.strength), args.steps), 0)
+    if args.scheduler == "pndm" and (begin or args.init_video):
+        ap.error("--scheduler pndm runs the whole schedule from noise: no --strength < 1, no --init-video")
     timesteps = sched.timesteps[begin:].tolist()
     if not timesteps:
         ap.error("--strength leaves no timestep to run")
@@ -155,7 +166,7 @@ def main():
             lat = torch.empty_like(init)
             extra["known"] = (init, inp["latents"], latent_m)
         else:
-            lat = inp["latents"] * pipe.scheduler.init_noise_sigma     # (1 but for Euler ancestral)
+            lat = inp["latents"] * pipe.scheduler.init_noise_sigma     # (1 but for the sigma schedulers)
         pipe.denoise(lat, kps_tokens, audio, timesteps, windows, args.guidance_scale, eta=eta, noise_seed=12345,
                      guidance_rescale=args.guidance_rescale, guidance_start=args.guidance_start,
                      guidance_end=args.guidance_end, **extra)
@@ -255,7 +266,8 @@ def main():
         finally:
             pipe.scheduler, eta = sched_a, eta_a
     print(json.dumps(dict(
-        scheduler=args.scheduler, order=args.order if args.scheduler == "dpm" else None,
+        scheduler=args.scheduler,
+        order=args.order if args.scheduler == "dpm" else args.lms_order if args.scheduler == "lms" else None,
         eta=eta if args.scheduler == "ddim-eta" else None, steps=args.steps,
         config=f"512x512, {F} frames ({'one window' if len(windows) == 1 else f'{len(windows)} windows'}), "
                f"CFG {args.guidance_scale:g}, synthetic weights, bf16",

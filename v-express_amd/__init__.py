@@ -7,7 +7,8 @@ There is no CPU/PyTorch fallback: importing the model classes loads libvexpress_
 is missing.  Host-only helpers (synth, context, scheduler, distributed) import without the library.
 """
 from .synth import UNetConfig, VaeConfig  # noqa: F401
-from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler  # noqa: F401
+from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
+                        EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler)
 
 _LAZY = {
     "UNet3DConditionModel": "unet_3d", "UNet3DConditionOutput": "unet_3d", "UNet2DConditionModel": "unet_2d",
@@ -26,4 +27,5 @@ def __getattr__(name):
 
 
 __all__ = ["UNetConfig", "VaeConfig", "DDIMScheduler", "DPMSolverMultistepScheduler",
-           "EulerAncestralDiscreteScheduler"] + list(_LAZY)
+           "EulerAncestralDiscreteScheduler", "EulerDiscreteScheduler", "LMSDiscreteScheduler",
+           "PNDMScheduler"] + list(_LAZY)

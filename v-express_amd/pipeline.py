@@ -32,7 +32,12 @@ from .distributed import (DistContext, MixedUnitSchedule, UnitSchedule, choose_f
 from .mutual_self_attention import ReferenceAttentionControl
 from .sampling import (ANCESTRAL, GUIDANCE_ROWS, Guidance, Known, Sampler, Stitch, UnitCall, ancestral_coefficients,
                        check_known)
-from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
+from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
+                        EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler)
+
+# the schedulers the loop drives besides DDIM, and the update each one runs (VExpressPipeline._sampler)
+_SAMPLER_OF = {DPMSolverMultistepScheduler: "dpm", EulerAncestralDiscreteScheduler: "euler-a",
+               EulerDiscreteScheduler: "euler", LMSDiscreteScheduler: "lms", PNDMScheduler: "pndm"}
 
 
 def _in_unet_element_type(fn):
@@ -91,6 +96,17 @@ def check_apg(apg, guidance_rescale=0.0):
         raise ValueError("apg_eta together with guidance_rescale > 0: both fight the same defect (the over-driven guided "
                          "prediction), and the combination is not built; pass one of them")
     return eta, r, beta
+
+
+def check_pndm_start(begin_index, has_init):
+    """PNDM's first two entries are a pair (an Euler step, redone from the saved sample): a run that starts inside the
+    schedule has none.  NotImplementedError for strength < 1 (begin_index != 0) or an init clip."""
+    if begin_index != 0:
+        raise NotImplementedError("PNDMScheduler: begin_index != 0 (strength < 1) is not built: the warm-up pair of "
+                                  "entries is not defined for a run that starts inside the schedule")
+    if has_init:
+        raise NotImplementedError("PNDMScheduler: init-video sampling (known / init_video / init_latents) is not built: "
+                                  "the warm-up pair of entries is not defined for a run that starts from a noised clip")
 
 
 def check_audio_guidance(audio_guidance_scale):
@@ -324,19 +340,22 @@ class VExpressPipeline:
     # ------------------------------------------------------------------ the hot loop
     def _sampler(self, eta=0.0):
         """The update the loop runs: "ddim" (vx_overlap_ddim_step), "ddim-eta" (DDIM with eta > 0), "dpm" (DPM-Solver++,
-        vx_overlap_multistep_step) or "euler-a" (Euler ancestral); the two ancestral ones run vx_overlap_ancestral_step.
+        vx_overlap_multistep_step), "euler-a" (Euler ancestral) - the two ancestral ones run vx_overlap_ancestral_step -
+        or "euler", "lms", "pndm" (Euler, LMS, PNDM: vx_overlap_linear_step).
         Any other scheduler raises TypeError before anything runs: the fused updates are the only ones the loop has.
         eta is honoured by DDIM only: eta != 0 with another scheduler raises NotImplementedError."""
         if isinstance(self.scheduler, DDIMScheduler):
             if eta < 0:
                 raise ValueError(f"eta must be >= 0, got {eta}")
             return "ddim" if eta == 0.0 else "ddim-eta"
-        if isinstance(self.scheduler, (DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler)):
-            if eta != 0.0:
-                raise NotImplementedError(f"eta != 0 is a DDIM option; {type(self.scheduler).__name__} does not take it")
-            return "dpm" if isinstance(self.scheduler, DPMSolverMultistepScheduler) else "euler-a"
+        for cls, kind in _SAMPLER_OF.items():
+            if isinstance(self.scheduler, cls):
+                if eta != 0.0:
+                    raise NotImplementedError(f"eta != 0 is a DDIM option; {type(self.scheduler).__name__} does not take it")
+                return kind
         raise TypeError(f"the denoising loop drives v_express_amd.DDIMScheduler or "
-                        f"v_express_amd.DPMSolverMultistepScheduler or v_express_amd.EulerAncestralDiscreteScheduler, "
+                        f"v_express_amd.DPMSolverMultistepScheduler or v_express_amd.EulerAncestralDiscreteScheduler or "
+                        f"v_express_amd.EulerDiscreteScheduler, LMSDiscreteScheduler or PNDMScheduler, "
                         f"not {type(self.scheduler).__name__}")
 
     def _unit_plan(self, latents, kps_tokens, audio, audio_is_zero, windows, win_ids, half_rows):
@@ -450,6 +469,11 @@ class VExpressPipeline:
         per frame.  Ancestral samplers (DDIM with eta > 0, Euler ancestral) draw the noise of step index i on the device
         from `noise_seed` (64 bits, required), keyed by (step index, frame, channel, pixel) only.  Euler ancestral: the
         latents come and go in the scheduler's (VE) frame; the loop runs in the VP frame x / sqrt(1 + sigma^2).
+        Euler, LMS and PNDM run one vx_overlap_linear_step per timestep (Euler and LMS in the VE frame like Euler
+        ancestral; LMS keeps eps of the last three steps per frame, PNDM the last model outputs and, for its warm-up
+        pair, one saved sample).  PNDM's timestep list has one entry more than num_inference_steps - the second timestep
+        twice - and every entry is one timestep of the loop (the guidance interval counts them); it cannot start inside
+        the schedule: begin_index != 0 or `known` raise NotImplementedError.
         Guidance controls (classifier-free guidance only; every sampler): step i of the N timesteps is guided iff
         i / N >= guidance_start and (i + 1) / N <= guidance_end, any other step computes the conditional rows only and
         takes them as the prediction; guidance_rescale = phi > 0 scales each window's guided prediction g by
@@ -496,6 +520,8 @@ class VExpressPipeline:
                                  f"index begin_index on")
         if kind in ANCESTRAL and noise_seed is None:
             raise ValueError(f"the {kind} sampler draws noise on the device: pass noise_seed")
+        if kind == "pndm":
+            check_pndm_start(begin_index, known is not None)
         unet, dc, dev = self.denoising_unet, self.dist, latents.device
         _, C, F, H, W = latents.shape
         hw = H * W
@@ -639,6 +665,8 @@ class VExpressPipeline:
         self.scheduler.set_timesteps(num_inference_steps)
         init_t = min(int(num_inference_steps * strength), num_inference_steps)
         begin_index = max(num_inference_steps - init_t, 0)
+        if kind == "pndm":
+            check_pndm_start(begin_index, init_video is not None or init_latents is not None)
         timesteps = self.scheduler.timesteps[begin_index:].tolist()
         if ancestral:
             ancestral_coefficients(self.scheduler, kind, timesteps, begin_index, eta)   # e.g. eta too large: ValueError here

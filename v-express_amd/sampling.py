@@ -3,7 +3,8 @@ buffers and host-side coefficients, so that a timestep reads straight down:
     UNet calls of guidance.plan(i) -> all_gather_units -> guidance.combine -> stitch.reduce -> sampler.update -> known.after
   Stitch    how the window predictions of a step become one prediction per frame: the mean plan, or the weighted pre-pass;
   Guidance  which rows a step runs per window and the one launch that combines them (rescaled or not);
-  Sampler   the update of the scheduler in use, its per-step coefficients and, for Euler ancestral, the VE <-> VP frame;
+  Sampler   the update of the scheduler in use, its per-step coefficients and, for the sigma (VE) schedulers - Euler
+            ancestral, Euler, LMS - the VE <-> VP frame;
   Known     the known region of init-video sampling: the start latents and the blend after every step.
 A choice that does not depend on the timestep is made in a constructor (a method bound there), never in the loop.  Every
 kernel wrapper is looked up as `ops.<name>` when it is called: tests and tools replace them there."""
@@ -15,6 +16,9 @@ from . import ops
 
 # the samplers that draw noise at every step (vx_overlap_ancestral_step)
 ANCESTRAL = ("ddim-eta", "euler-a")
+# the linear multistep samplers (vx_overlap_linear_step), and the samplers whose scheduler works in the VE frame
+LINEAR = ("euler", "lms", "pndm")
+VE_FRAME = ("euler-a", "euler", "lms")
 
 # The batch rows a window can run, as (bank row, keypoint row, audio row) of the CFG-layout conditioning (row 0 zeros,
 # row 1 real): "u" drops everything, "m" ("silent") keeps the reference bank and the keypoints and drops the audio, "c"
@@ -162,15 +166,25 @@ class Guidance:
 
 class Sampler:
     """The update of one frame set per timestep: "ddim" (vx_overlap_ddim_step), "dpm" (vx_overlap_multistep_step, with the
-    previous step's x0 of every frame in `x0_hist`: identical on every rank, like the latents) or an ancestral one
-    (vx_overlap_ancestral_step, noise keyed by `noise_seed` and the step index).  The coefficients of every step are
-    resolved on the host here.  Euler ancestral: the latents come and go in the scheduler's (VE) frame and the loop runs
-    in the VP frame x / sqrt(1 + sigma^2); `frame_scale` is the scheduler's, None for the others."""
+    previous step's x0 of every frame in `x0_hist`: identical on every rank, like the latents), an ancestral one
+    (vx_overlap_ancestral_step, noise keyed by `noise_seed` and the step index) or a linear multistep one - "euler", "lms",
+    "pndm" (vx_overlap_linear_step, with `history`, three per-frame slots, and `saved`, PNDM's saved sample: allocated
+    only when some step names them, never read before they are written, identical on every rank).  The coefficients of
+    every step are resolved on the host here.  Euler ancestral, Euler, LMS: the latents come and go in the scheduler's
+    (VE) frame and the loop runs in the VP frame x / sqrt(1 + sigma^2); `frame_scale` is the scheduler's, None for the
+    others."""
 
     def __init__(self, scheduler, kind, latents, timesteps, begin_index, eta, noise_seed):
         self.begin_index, self.steps = begin_index, len(timesteps)
-        self.frame_scale = scheduler.frame_scale if kind == "euler-a" and timesteps else None
-        if kind == "dpm":
+        self.frame_scale = scheduler.frame_scale if kind in VE_FRAME and timesteps else None
+        if kind in LINEAR:
+            self.coefs = [scheduler.linear_coefficients(begin_index + i, begin_index) for i in range(self.steps)]
+            slots = any(max(cf[:4]) >= 0 for cf in self.coefs)
+            self.history = torch.empty((3,) + tuple(latents.shape[1:]), device=latents.device,
+                                       dtype=torch.float32) if slots else None
+            self.saved = torch.empty_like(latents) if any(cf.saved_mode for cf in self.coefs) else None
+            self._update = self._linear
+        elif kind == "dpm":
             self.x0_hist = torch.empty_like(latents)
             self.coefs = [scheduler.multistep_coefficients(begin_index + i, begin_index) for i in range(self.steps)]
             self._update = self._multistep
@@ -201,8 +215,12 @@ class Sampler:
         ops.overlap_ancestral_step(latents, step_preds, stitch.terms, stitch.frame_ids, stitch.counts, self.coefs[i],
                                    self.noise_seed, self.begin_index + i)
 
+    def _linear(self, i, latents, step_preds, stitch):
+        ops.overlap_linear_step(latents, step_preds, stitch.terms, stitch.frame_ids, stitch.counts, self.history,
+                                self.saved, self.coefs[i])
+
     def callback_view(self, i, latents):
-        """What a callback sees after step i: the scheduler's own (VE) frame for Euler ancestral, as the reference's."""
+        """What a callback sees after step i: the scheduler's own (VE) frame for the sigma schedulers, as the reference's."""
         if self.frame_scale is None:
             return latents
         return latents * self.frame_scale(self.begin_index + i + 1)
@@ -232,7 +250,7 @@ def check_known(known, latents):
 class Known:
     """Init-video sampling: (init, noise, mask) of check_known and the scheduler's (a, s) of the start and of the blend
     after every step, resolved on the host.  `start` forms the start latents a_b init + s_b noise in the frame the loop
-    runs in (Euler ancestral: the VP frame, (init + sigma noise) / sqrt(1 + sigma^2)); `after` puts the kept part back at
+    runs in (the sigma schedulers: the VP frame, (init + sigma noise) / sqrt(1 + sigma^2)); `after` puts the kept part back at
     the level the latents have after step i (init itself after the last step) - with a mask only.  `report` is last_init."""
 
     def __init__(self, scheduler, init, noise, mask, steps, begin_index):

@@ -8,10 +8,13 @@ Host side only: the per-step update itself runs in the fused `vx_overlap_ddim_st
 second-order multistep sampler of the reference's scheduler list, pipelines/v_express_pipeline.py:83-90) feeds
 `vx_overlap_multistep_step` the same way through `multistep_coefficients(i)`.  The ancestral samplers (DDIM with
 eta > 0 through `DDIMScheduler.ancestral_coefficients(t, eta)`, EulerAncestralDiscreteScheduler through
-`ancestral_coefficients(i)`) feed `vx_overlap_ancestral_step`, which draws its noise on the device.
+`ancestral_coefficients(i)`) feed `vx_overlap_ancestral_step`, which draws its noise on the device.  The rest of the
+reference's list - EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler - are linear multistep updates in the loop's
+frame and feed `vx_overlap_linear_step` through `linear_coefficients(i, begin_index)`.
 """
 from types import SimpleNamespace
 
+import collections
 import math
 
 import numpy as np
@@ -467,3 +470,430 @@ class EulerAncestralDiscreteScheduler:
         self._step_index += 1
         out = SimpleNamespace(prev_sample=prev, pred_original_sample=x0)
         return out if return_dict else (prev,)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Linear multistep samplers (Euler discrete, LMS discrete, PNDM): one update form in the loop's variance-preserving frame,
+#     b = saved if saved_mode == 2 else x;   out = k_x b + k_v v + c_1 H[h1] + c_2 H[h2] + c_3 H[h3]
+# over the latents x, the window-averaged model output v, up to three per-frame history tensors H (a ring of three slots;
+# the entry a step writes is p_x x + p_v v) and, for PNDM's warm-up pair, one saved sample.  The fused
+# `vx_overlap_linear_step` kernel runs it, fed by each class's `linear_coefficients(i, begin_index)`.
+LinearStep = collections.namedtuple("LinearStep", "h1 h2 h3 h_write saved_mode k_x k_v c_1 c_2 c_3 p_x p_v")
+LinearStep.__doc__ = """Coefficients of one linear multistep update: history slots read (h1..h3) and written (h_write), each
+0..2 or -1 (none); saved_mode 0 (no saved sample), 1 (store x) or 2 (the saved sample is the base b);
+out = k_x b + k_v v + sum_j c_j H[h_j]; the history entry written is p_x x + p_v v."""
+
+
+def _linear_step(k_x, k_v, reads=(), h_write=-1, saved_mode=0, p=(0.0, 0.0)):
+    """LinearStep from (slot, coefficient) pairs of the history terms, in the order they are added."""
+    slots = [sl for sl, _ in reads] + [-1] * (3 - len(reads))
+    cs = [float(cj) for _, cj in reads] + [0.0] * (3 - len(reads))
+    return LinearStep(*slots, h_write, saved_mode, float(k_x), float(k_v), *cs, float(p[0]), float(p[1]))
+
+
+def lms_integrals(sg, i, order):
+    """[L_0 .. L_{order-1}] of step index i: L_j = integral from sg[i] to sg[i + 1] of the Lagrange basis polynomial
+    prod_{k != j, k < order} (tau - sg[i - k]) / (sg[i - j] - sg[i - k]) - the weights of diffusers'
+    LMSDiscreteScheduler.get_lms_coefficient, integrated here as an exact polynomial in float64 (diffusers:
+    scipy.integrate.quad with epsrel = 1e-4).  In the variable u = tau - sg[i] the lower limit is 0, so the antiderivative
+    is evaluated once, at u = sg[i + 1] - sg[i]."""
+    nodes = [float(sg[i - k]) - float(sg[i]) for k in range(order)]
+    upper = float(sg[i + 1]) - float(sg[i])
+    out = []
+    for j in range(order):
+        coef = [1.0]                                             # the basis polynomial in u, ascending powers
+        for k in range(order):
+            if k != j:
+                d, nxt = nodes[j] - nodes[k], [0.0] * (len(coef) + 1)
+                for p, cp in enumerate(coef):                    # times (u - nodes[k]) / d
+                    nxt[p + 1] += cp / d
+                    nxt[p] -= cp * nodes[k] / d
+                coef = nxt
+        out.append(sum(cp * upper ** (p + 1) / (p + 1) for p, cp in enumerate(coef)))
+    return out
+
+
+class _SigmaScheduler:
+    """What the two deterministic samplers of the sigma (VE) parametrisation share with EulerAncestralDiscreteScheduler:
+    the clamped zero-SNR table, sigmas = table[timesteps] + [0], init_noise_sigma = the largest sigma, the UNet input
+    x / sqrt(1 + sigma^2), and the VP pair and frame scale the loop asks for."""
+    order = 1
+
+    def _tables(self, num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr):
+        self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
+        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, 0)
+        if rescale_betas_zero_snr:
+            # the zero-SNR table ends at alphas_cumprod = 0: clamped so that the first sigma is finite (4096)
+            self.alphas_cumprod[-1] = 2 ** -24
+        # sigma(t) = sqrt((1 - abar_t) / abar_t) in float32, as diffusers computes it
+        self.sigma_table = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
+        self.sigmas = torch.cat([self.sigma_table.flip(0), torch.zeros(1)]).to(torch.float32)
+        self.timesteps = torch.linspace(0, num_train_timesteps - 1, num_train_timesteps,
+                                        dtype=torch.float64).flip(0).to(torch.float32)
+        self.num_inference_steps = None
+        self._reset()
+
+    @classmethod
+    def from_config(cls, cfg, **overrides):
+        """From a dict or another scheduler's `config` (e.g. `DDIMScheduler(...).config`)."""
+        cfg = dict(cfg) if isinstance(cfg, dict) else dict(vars(cfg))
+        cfg.update(overrides)
+        return cls(**cfg)
+
+    def _reset(self):
+        self._step_index = None
+        self._begin_index = None
+        self._taken = 0
+        self._derivatives = []
+
+    @property
+    def init_noise_sigma(self):
+        """diffusers: the largest sigma under "linspace" / "trailing" spacing (a float32 tensor)."""
+        return self.sigmas.max()
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    @property
+    def begin_index(self):
+        return self._begin_index
+
+    def set_begin_index(self, begin_index=0):
+        self._begin_index = begin_index
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        T = self.config.num_train_timesteps
+        self.num_inference_steps = num_inference_steps
+        ts = np.arange(T, 0, -T / num_inference_steps).round().astype(np.float32) - 1
+        self.timesteps = torch.from_numpy(ts.copy())
+        sig = self.sigma_table[self.timesteps.long()]
+        self.sigmas = torch.cat([sig, torch.zeros(1)]).to(torch.float32)
+        self._reset()
+
+    def _init_step_index(self, timestep):
+        if self._begin_index is not None:
+            self._step_index = self._begin_index
+            return
+        hits = (self.timesteps == float(timestep)).nonzero()
+        if len(hits) == 0:
+            raise ValueError(f"timestep {float(timestep)} is not in this schedule")
+        self._step_index = int(hits[1 if len(hits) > 1 else 0])
+
+    def scale_model_input(self, sample, timestep=None):
+        """x_ve -> x_vp = x_ve / sqrt(1 + sigma^2) at the current step (diffusers' scaling of the UNet input)."""
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        sigma = self.sigmas[self._step_index]
+        return sample / ((sigma ** 2 + 1) ** 0.5)
+
+    def _check_index(self, i, begin_index=0, closed=False):
+        n = self.num_inference_steps
+        if n is None:
+            raise RuntimeError("call set_timesteps() first")
+        if not begin_index <= i < n + (1 if closed else 0):
+            raise IndexError(f"step index {i} outside [{begin_index}, {n}{']' if closed else ')'}")
+
+    def _vp(self, j):
+        """(a, s) = (1, sigma) / sqrt(1 + sigma^2) of sigmas[j], in float64."""
+        sg = float(self.sigmas[j])
+        a = 1.0 / math.sqrt(sg * sg + 1.0)
+        return a, sg * a
+
+    def noise_coefficients(self, j):
+        """(a_j, s_j) = (1, sigma_j) / sqrt(1 + sigma_j^2) of sigmas[j]: the variance-preserving pair of the frame the
+        loop runs in (x_vp = x_ve / sqrt(1 + sigma^2)); j = number of steps: the final sigma = 0, (1, 0)."""
+        self._check_index(j, closed=True)
+        return self._vp(j)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' add_noise in the scheduler's own (VE) frame: x0 + sigma noise at the schedule's own timesteps (one,
+        or one per sample of the batch)."""
+        own = [float(t) for t in self.timesteps.tolist()]
+        sig = []
+        for t in _timestep_list(timesteps):
+            if t not in own:
+                raise ValueError(f"timestep {t} is not in this schedule")
+            sig.append(float(self.sigmas[own.index(t)]))
+        return original_samples + _per_sample(sig, original_samples) * noise
+
+    def frame_scale(self, i):
+        """sqrt(1 + sigmas[i]^2): x_ve = frame_scale(i) x_vp at step index i (1 at the final sigma = 0)."""
+        s = float(self.sigmas[i])
+        return math.sqrt(1.0 + s * s)
+
+    def _derivative(self, model_output, sample, i):
+        """diffusers' v-prediction arithmetic in the VE frame: (x0, d = (x - x0) / sigma = eps), float64 scalars."""
+        sigma = float(self.sigmas[i])
+        x0 = model_output * (-sigma / math.sqrt(sigma * sigma + 1.0)) + sample / (sigma * sigma + 1.0)
+        return x0, (sample - x0) / sigma
+
+
+class EulerDiscreteScheduler(_SigmaScheduler):
+    """Euler sampling for the zero-terminal-SNR v-prediction schedule: the arithmetic of diffusers==0.29.2
+    `EulerDiscreteScheduler` restated for the options listed in `__init__` (any other value raises NotImplementedError
+    naming the option; `step(..., s_churn != 0)` too).
+
+    diffusers works in the VE frame (x_ve = x0 + sigma eps, `scale_model_input` divides by sqrt(1 + sigma^2)); the loop runs
+    in the VP frame x_vp = x_ve / sqrt(1 + sigma^2) - exactly the UNet input - with `vx_overlap_linear_step`, fed by
+    `linear_coefficients(i)`.  With a = 1 / sqrt(1 + sigma_i^2), s = sigma_i a and primes for i + 1:
+        x0 = a x - s v,  eps = s x + a v,  x' = a' x0 + s' eps = (a' a + s' s) x + (s' a - a' s) v
+    (the deterministic DDIM update between the two sigmas).  `step()` is the stateful diffusers-style tensor API in the VE
+    frame."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 trained_betas=None, prediction_type="epsilon", interpolation_type="linear", use_karras_sigmas=False,
+                 sigma_min=None, sigma_max=None, timestep_spacing="linspace", timestep_type="discrete", steps_offset=0,
+                 rescale_betas_zero_snr=False, final_sigmas_type="zero", **unused):
+        # (clip_sample, set_alpha_to_one, ... of a DDIM configuration are not parameters of this sampler: ignored, as
+        # diffusers' from_config does)
+        for name, value, ok in (("trained_betas", trained_betas, trained_betas is None),
+                                ("beta_schedule", beta_schedule, beta_schedule in ("linear", "scaled_linear")),
+                                ("prediction_type", prediction_type, prediction_type == "v_prediction"),
+                                ("interpolation_type", interpolation_type, interpolation_type == "linear"),
+                                ("use_karras_sigmas", use_karras_sigmas, not use_karras_sigmas),
+                                ("sigma_min", sigma_min, sigma_min is None),
+                                ("sigma_max", sigma_max, sigma_max is None),
+                                ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing"),
+                                ("timestep_type", timestep_type, timestep_type == "discrete"),
+                                ("final_sigmas_type", final_sigmas_type, final_sigmas_type == "zero")):
+            if not ok:
+                raise NotImplementedError(f"EulerDiscreteScheduler: {name}={value!r} is not built")
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, prediction_type=prediction_type,
+                                      interpolation_type=interpolation_type, use_karras_sigmas=use_karras_sigmas,
+                                      timestep_spacing=timestep_spacing, timestep_type=timestep_type,
+                                      steps_offset=steps_offset, rescale_betas_zero_snr=rescale_betas_zero_snr,
+                                      final_sigmas_type=final_sigmas_type)
+        self._tables(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
+
+    def linear_coefficients(self, i, begin_index=0):
+        """LinearStep of step index i: k_x = a' a + s' s, k_v = s' a - a' s, no history.  Float64 arithmetic on the
+        float32 sigmas; a step that ends at sigma = 0 is x0 itself, (k_x, k_v) = (a, -s)."""
+        self._check_index(i, begin_index)
+        (a, s), (a1, s1) = self._vp(i), self._vp(i + 1)
+        return _linear_step(a1 * a + s1 * s, s1 * a - a1 * s)
+
+    def step(self, model_output, timestep, sample, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0,
+             generator=None, return_dict=True, **unused):
+        """One update on tensors in the VE frame (v-prediction `model_output`): x + d (sigma' - sigma), keeping the step
+        index like diffusers."""
+        if s_churn != 0.0:
+            raise NotImplementedError(f"EulerDiscreteScheduler.step: s_churn={s_churn!r} is not built")
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        i = self._step_index
+        x0, d = self._derivative(model_output, sample, i)
+        prev = sample + d * (float(self.sigmas[i + 1]) - float(self.sigmas[i]))
+        self._step_index += 1
+        out = SimpleNamespace(prev_sample=prev, pred_original_sample=x0)
+        return out if return_dict else (prev,)
+
+
+class LMSDiscreteScheduler(_SigmaScheduler):
+    """Linear multistep (Adams-Bashforth on the sigma grid) sampling for the zero-terminal-SNR v-prediction schedule: the
+    arithmetic of diffusers==0.29.2 `LMSDiscreteScheduler` restated for the options listed in `__init__` (any other value
+    raises NotImplementedError naming the option).  `lms_order` (1..4, default 4: the `order=4` default of diffusers'
+    `step`) is this project's keyword - the loop cannot pass `order` to a step; the class attribute `order` stays 1 (the
+    reference reads it, pipelines/v_express_pipeline.py:582).  `rescale_betas_zero_snr` is this project's too (diffusers'
+    class has no such keyword): the reference's noise_scheduler_kwargs pass unchanged.
+
+    diffusers: X' = X + sum_j L_j d_{i-j} in the VE frame, d = eps, L_j = `lms_integrals` (here exact; diffusers
+    integrates numerically to 1e-4).  In the VP frame of the loop, with E = sigma_i + L_0 formed as
+    sigma_{i+1} - sum_{j>=1} L_j:
+        x' = a' (a + E s) x + a' (E a - s) v + sum_{j>=1} a' L_j eps_{i-j},   eps_i = s x + a v
+    with eps kept per frame in a ring of three slots - `linear_coefficients(i, begin_index)` for `vx_overlap_linear_step`.
+    `step()` is the stateful diffusers-style tensor API in the VE frame."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 trained_betas=None, use_karras_sigmas=False, prediction_type="epsilon", timestep_spacing="linspace",
+                 steps_offset=0, rescale_betas_zero_snr=False, lms_order=4, **unused):
+        for name, value, ok in (("trained_betas", trained_betas, trained_betas is None),
+                                ("beta_schedule", beta_schedule, beta_schedule in ("linear", "scaled_linear")),
+                                ("use_karras_sigmas", use_karras_sigmas, not use_karras_sigmas),
+                                ("prediction_type", prediction_type, prediction_type == "v_prediction"),
+                                ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing"),
+                                ("lms_order", lms_order, lms_order in (1, 2, 3, 4))):
+            if not ok:
+                raise NotImplementedError(f"LMSDiscreteScheduler: {name}={value!r} is not built")
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, use_karras_sigmas=use_karras_sigmas,
+                                      prediction_type=prediction_type, timestep_spacing=timestep_spacing,
+                                      steps_offset=steps_offset, rescale_betas_zero_snr=rescale_betas_zero_snr,
+                                      lms_order=lms_order)
+        self._tables(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
+
+    def order_at(self, i, begin_index=0):
+        """min(i - begin_index + 1, lms_order): the number of derivatives the update of step index i combines in a run
+        that started at `begin_index` (the history starts empty there)."""
+        self._check_index(i, begin_index)
+        return min(i - begin_index + 1, self.config.lms_order)
+
+    def lms_coefficients(self, i, begin_index=0):
+        """[L_0 .. L_{o-1}] of step index i, o = order_at(i, begin_index)."""
+        return lms_integrals(self.sigmas.tolist(), i, self.order_at(i, begin_index))
+
+    def linear_coefficients(self, i, begin_index=0):
+        """LinearStep of step index i of a run that started at `begin_index`.  eps_{i-j} is read from ring slot
+        (i - begin_index - j) % 3 and eps_i written to slot (i - begin_index) % 3 - at fourth order the slot of
+        eps_{i-3}, read by the same update.  lms_order 1 keeps no history."""
+        L = self.lms_coefficients(i, begin_index)
+        (a, s), (a1, _) = self._vp(i), self._vp(i + 1)
+        E = float(self.sigmas[i + 1]) - sum(L[1:])                 # sigma_i + L_0
+        r = i - begin_index
+        reads = [((r - j) % 3, a1 * L[j]) for j in range(1, len(L))]
+        return _linear_step(a1 * (a + E * s), a1 * (E * a - s), reads,
+                            h_write=r % 3 if self.config.lms_order > 1 else -1, p=(s, a))
+
+    def step(self, model_output, timestep, sample, order=None, return_dict=True, **unused):
+        """One update on tensors in the VE frame (v-prediction `model_output`), keeping the step index and the last
+        derivatives like diffusers; `order` defaults to lms_order."""
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        i = self._step_index
+        order = self.config.lms_order if order is None else int(order)
+        x0, d = self._derivative(model_output, sample, i)
+        self._derivatives = (self._derivatives + [d])[-order:]
+        L = lms_integrals(self.sigmas.tolist(), i, min(len(self._derivatives), order))
+        prev = sample + sum(lj * dj for lj, dj in zip(L, reversed(self._derivatives)))
+        self._step_index += 1
+        out = SimpleNamespace(prev_sample=prev, pred_original_sample=x0)
+        return out if return_dict else (prev,)
+
+
+# the Adams-Bashforth weights of diffusers' PNDMScheduler.step_plms by the number of stored outputs (newest first)
+_PLMS = {1: (1.0,), 2: (3 / 2, -1 / 2), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}
+
+
+class PNDMScheduler:
+    """PNDM's linear multistep part (PLMS) for the zero-terminal-SNR v-prediction schedule: the arithmetic of
+    diffusers==0.29.2 `PNDMScheduler` with `skip_prk_steps=True`, restated for the options listed in `__init__` (any other
+    value raises NotImplementedError naming the option - diffusers' default skip_prk_steps=False, the Runge-Kutta warm-up,
+    among them).  `rescale_betas_zero_snr` is this project's keyword (diffusers' class has none): the reference's
+    noise_scheduler_kwargs pass unchanged; the table needs no clamp, see `_transfer`.
+
+    `set_timesteps(N)` gives N + 1 entries, the second timestep twice: entry 0 is an Euler step whose sample is saved,
+    entry 1 redoes it from the saved sample with the mean of the two outputs, entries 2, 3, >= 4 are Adams-Bashforth of
+    order 2, 3, 4 over the stored outputs.  The loop runs it with `vx_overlap_linear_step`, fed by
+    `linear_coefficients(n)`; `step()` is the stateful diffusers-style tensor API."""
+    order = 1
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 trained_betas=None, skip_prk_steps=False, set_alpha_to_one=False, prediction_type="epsilon",
+                 timestep_spacing="leading", steps_offset=0, rescale_betas_zero_snr=False, **unused):
+        for name, value, ok in (("trained_betas", trained_betas, trained_betas is None),
+                                ("beta_schedule", beta_schedule, beta_schedule in ("linear", "scaled_linear")),
+                                ("skip_prk_steps", skip_prk_steps, bool(skip_prk_steps)),
+                                ("prediction_type", prediction_type, prediction_type == "v_prediction"),
+                                ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing")):
+            if not ok:
+                raise NotImplementedError(f"PNDMScheduler: {name}={value!r} is not built")
+        self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
+        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, 0)
+        self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, skip_prk_steps=skip_prk_steps,
+                                      set_alpha_to_one=set_alpha_to_one, prediction_type=prediction_type,
+                                      timestep_spacing=timestep_spacing, steps_offset=steps_offset,
+                                      rescale_betas_zero_snr=rescale_betas_zero_snr)
+        self.init_noise_sigma = 1.0
+        self.pndm_order = 4
+        self.num_inference_steps = None
+        self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1)
+        self._reset()
+
+    @classmethod
+    def from_config(cls, cfg, **overrides):
+        """From a dict or another scheduler's `config` (e.g. `DDIMScheduler(...).config`)."""
+        cfg = dict(cfg) if isinstance(cfg, dict) else dict(vars(cfg))
+        cfg.update(overrides)
+        return cls(**cfg)
+
+    def _reset(self):
+        self.counter = 0
+        self.ets = []
+        self.cur_sample = None
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        """diffusers' plms_timesteps under skip_prk_steps: with t the ascending trailing list,
+        reverse(t[:-1] + t[-2:-1] + t[-1:]) - N + 1 entries for N >= 2, the second one repeated."""
+        T = self.config.num_train_timesteps
+        self.num_inference_steps = num_inference_steps
+        t = (np.round(np.arange(T, 0, -T / num_inference_steps))[::-1].astype(np.int64) - 1)
+        ts = np.concatenate([t[:-1], t[-2:-1], t[-1:]])[::-1].copy()
+        self.timesteps = torch.from_numpy(ts)
+        self._reset()
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def _abar(self, t):
+        return float(self.alphas_cumprod[t]) if t >= 0 else float(self.final_alpha_cumprod)
+
+    def _transfer(self, t_from, t_to):
+        """(k_x, g) of diffusers' _get_prev_sample between two timesteps, x' = k_x b + g vc.  diffusers writes it
+        sqrt(ap / a) b - (ap - a)(sqrt(a) vc + sqrt(1 - a) b) / (a sqrt(1 - ap) + sqrt(a (1 - a) ap)) on the cumulative
+        alphas a (from) and ap (to), 0 / 0 at a = 0; the same map is the rotation used here,
+        k_x = al' al + s' s, g = s' al - al' s with al = sqrt(a), s = sqrt(1 - a), finite on the unclamped zero-SNR table."""
+        a, ap = self._abar(t_from), self._abar(t_to)
+        al, s, al1, s1 = math.sqrt(a), math.sqrt(1.0 - a), math.sqrt(ap), math.sqrt(1.0 - ap)
+        return al1 * al + s1 * s, s1 * al - al1 * s
+
+    def _entry(self, n):
+        if self.num_inference_steps is None:
+            raise RuntimeError("call set_timesteps() first")
+        if not 0 <= n < len(self.timesteps):
+            raise IndexError(f"entry {n} outside [0, {len(self.timesteps)})")
+        t, r = int(self.timesteps[n]), self.config.num_train_timesteps // self.num_inference_steps
+        return (t + r, t) if n == 1 else (t, t - r)
+
+    def linear_coefficients(self, n, begin_index=0):
+        """LinearStep of entry n (diffusers' `counter`) of the timestep list.  The history holds the averaged model
+        output itself, (p_x, p_v) = (0, 1); the k-th output stored (entry 0, then entries 2, 3, ...) goes to ring slot
+        k % 3 - at fourth order the slot of the oldest one, read by the same update."""
+        if begin_index != 0:
+            raise NotImplementedError("PNDMScheduler: begin_index != 0 (strength < 1): the warm-up pair of entries is not "
+                                      "defined for a run that starts inside the schedule")
+        k_x, g = self._transfer(*self._entry(n))
+        if n == 0:
+            return _linear_step(k_x, g, h_write=0, saved_mode=1, p=(0.0, 1.0))
+        if n == 1:
+            return _linear_step(k_x, 0.5 * g, [(0, 0.5 * g)], saved_mode=2, p=(0.0, 1.0))
+        k = n - 1                                      # this entry's output is the k-th one stored
+        w = _PLMS[min(k + 1, 4)]
+        reads = [((k - j) % 3, g * w[j]) for j in range(1, len(w))]
+        return _linear_step(k_x, g * w[0], reads, h_write=k % 3, p=(0.0, 1.0))
+
+    def noise_coefficients(self, j):
+        """(a_j, s_j) = (sqrt(abar), sqrt(1 - abar)) of timesteps[j], the level the latents have at entry j;
+        j = len(timesteps): the level after the last entry (final_alpha_cumprod)."""
+        n = len(self.timesteps)
+        if not 0 <= j <= n:
+            raise IndexError(f"entry {j} outside [0, {n}]")
+        abar = self._abar(int(self.timesteps[j]) if j < n else -1)
+        return math.sqrt(abar), math.sqrt(1.0 - abar)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' PNDMScheduler.add_noise: sqrt(abar_t) x0 + sqrt(1 - abar_t) noise, t one timestep or one per sample
+        of the batch."""
+        abar = [float(self.alphas_cumprod[int(t)]) for t in _timestep_list(timesteps)]
+        a = _per_sample([math.sqrt(v) for v in abar], original_samples)
+        s = _per_sample([math.sqrt(1.0 - v) for v in abar], original_samples)
+        return a * original_samples + s * noise
+
+    def step(self, model_output, timestep, sample, return_dict=True, **unused):
+        """diffusers' step_plms on tensors (v-prediction `model_output`), keeping `counter`, `ets` and `cur_sample`."""
+        n = self.counter
+        k_x, g = self._transfer(*self._entry(n))
+        if n != 1:
+            self.ets = self.ets[-3:] + [model_output]
+        if n == 0:
+            combined, self.cur_sample = model_output, sample
+        elif n == 1:
+            combined, sample, self.cur_sample = (model_output + self.ets[-1]) / 2, self.cur_sample, None
+        else:
+            w = _PLMS[len(self.ets)]
+            combined = sum(wj * e for wj, e in zip(w, reversed(self.ets)))
+        prev = k_x * sample + g * combined
+        self.counter += 1
+        return SimpleNamespace(prev_sample=prev) if return_dict else (prev,)
