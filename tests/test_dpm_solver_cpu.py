@@ -104,6 +104,7 @@ def test_options_and_construction():
     s = DPMSolverMultistepScheduler(**D.KWARGS)           # inference_v2.yaml's noise_scheduler_kwargs, unchanged
     assert (s.config.solver_order, s.config.final_sigmas_type, s.init_noise_sigma, s.order) == (2, "zero", 1.0, 1)
     ddim = DDIMScheduler(**D.KWARGS)
+    assert torch.equal(DDIMScheduler.from_config(ddim.config).alphas_cumprod, ddim.alphas_cumprod)
     for src in (ddim.config, dict(D.KWARGS)):
         f = DPMSolverMultistepScheduler.from_config(src)
         f.set_timesteps(15)

@@ -30,14 +30,8 @@ from .context import blend_weights, check_blend, get_context_scheduler, overlap_
 from .distributed import (DistContext, MixedUnitSchedule, UnitSchedule, choose_frame_shards, choose_mixed_shards,
                           split_frames)
 from .mutual_self_attention import ReferenceAttentionControl
-from .sampling import (ANCESTRAL, GUIDANCE_ROWS, Guidance, Known, Sampler, Stitch, UnitCall, ancestral_coefficients,
-                       check_known)
-from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
-                        EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler)
-
-# the schedulers the loop drives besides DDIM, and the update each one runs (VExpressPipeline._sampler)
-_SAMPLER_OF = {DPMSolverMultistepScheduler: "dpm", EulerAncestralDiscreteScheduler: "euler-a",
-               EulerDiscreteScheduler: "euler", LMSDiscreteScheduler: "lms", PNDMScheduler: "pndm"}
+from .sampling import GUIDANCE_ROWS, Guidance, Known, Sampler, Stitch, UnitCall, check_known
+from .scheduler import _Scheduler
 
 
 def _in_unet_element_type(fn):
@@ -96,17 +90,6 @@ def check_apg(apg, guidance_rescale=0.0):
         raise ValueError("apg_eta together with guidance_rescale > 0: both fight the same defect (the over-driven guided "
                          "prediction), and the combination is not built; pass one of them")
     return eta, r, beta
-
-
-def check_pndm_start(begin_index, has_init):
-    """PNDM's first two entries are a pair (an Euler step, redone from the saved sample): a run that starts inside the
-    schedule has none.  NotImplementedError for strength < 1 (begin_index != 0) or an init clip."""
-    if begin_index != 0:
-        raise NotImplementedError("PNDMScheduler: begin_index != 0 (strength < 1) is not built: the warm-up pair of "
-                                  "entries is not defined for a run that starts inside the schedule")
-    if has_init:
-        raise NotImplementedError("PNDMScheduler: init-video sampling (known / init_video / init_latents) is not built: "
-                                  "the warm-up pair of entries is not defined for a run that starts from a noised clip")
 
 
 def check_audio_guidance(audio_guidance_scale):
@@ -339,24 +322,17 @@ class VExpressPipeline:
 
     # ------------------------------------------------------------------ the hot loop
     def _sampler(self, eta=0.0):
-        """The update the loop runs: "ddim" (vx_overlap_ddim_step), "ddim-eta" (DDIM with eta > 0), "dpm" (DPM-Solver++,
-        vx_overlap_multistep_step), "euler-a" (Euler ancestral) - the two ancestral ones run vx_overlap_ancestral_step -
-        or "euler", "lms", "pndm" (Euler, LMS, PNDM: vx_overlap_linear_step).
-        Any other scheduler raises TypeError before anything runs: the fused updates are the only ones the loop has.
-        eta is honoured by DDIM only: eta != 0 with another scheduler raises NotImplementedError."""
-        if isinstance(self.scheduler, DDIMScheduler):
-            if eta < 0:
-                raise ValueError(f"eta must be >= 0, got {eta}")
-            return "ddim" if eta == 0.0 else "ddim-eta"
-        for cls, kind in _SAMPLER_OF.items():
-            if isinstance(self.scheduler, cls):
-                if eta != 0.0:
-                    raise NotImplementedError(f"eta != 0 is a DDIM option; {type(self.scheduler).__name__} does not take it")
-                return kind
-        raise TypeError(f"the denoising loop drives v_express_amd.DDIMScheduler or "
-                        f"v_express_amd.DPMSolverMultistepScheduler or v_express_amd.EulerAncestralDiscreteScheduler or "
-                        f"v_express_amd.EulerDiscreteScheduler, LMSDiscreteScheduler or PNDMScheduler, "
-                        f"not {type(self.scheduler).__name__}")
+        """The fused update the loop runs with this scheduler and eta - "ddim", "multistep", "ancestral" or "linear", the
+        scheduler's own answer (scheduler.loop_steps, here for a run of no steps; the caller asks again with its
+        timesteps for the coefficients).  Any scheduler that is not one of the project's raises TypeError before anything
+        runs: the fused updates are the only ones the loop has.  eta is honoured by DDIM only: the others raise
+        NotImplementedError."""
+        if not isinstance(self.scheduler, _Scheduler):
+            raise TypeError(f"the denoising loop drives v_express_amd.DDIMScheduler or "
+                            f"v_express_amd.DPMSolverMultistepScheduler or v_express_amd.EulerAncestralDiscreteScheduler or "
+                            f"v_express_amd.EulerDiscreteScheduler, LMSDiscreteScheduler or PNDMScheduler, "
+                            f"not {type(self.scheduler).__name__}")
+        return self.scheduler.loop_steps((), 0, eta)[0]
 
     def _unit_plan(self, latents, kps_tokens, audio, audio_is_zero, windows, win_ids, half_rows):
         """The static plan of one kind of timestep: which (window, half) units this rank computes, in which UNet calls,
@@ -504,24 +480,24 @@ class VExpressPipeline:
         update then runs on that buffer with the trivial plan (one term, count 1), so x0 history, noise stream and the
         known-region blend are what they are on the mean route.  The windows must not hold a frame twice ("linear":
         contiguous runs by increasing start), which context_schedule="uniform_fit" gives for any clip length."""
-        kind = self._sampler(eta)
+        update = self._sampler(eta)
         blend_kind = check_blend(overlap_blend, len(windows[0]))
         raw_weights = None if blend_kind == "mean" else blend_weights(windows, overlap_blend)
         guidance_rescale, guided = check_guidance(guidance_rescale, guidance_start, guidance_end, len(timesteps))
         row_names = guidance_rows(guidance_scale, audio_guidance_scale)
         apg = check_apg(apg, guidance_rescale)
         init, noise, kmask = check_known(known, latents)
-        if kind != "ddim" or known is not None:
+        if update != "ddim" or known is not None:
             all_ts = [int(t) for t in self.scheduler.timesteps.tolist()]
             if begin_index is None:
                 begin_index = len(all_ts) - len(timesteps)
             if [int(t) for t in timesteps] != all_ts[begin_index:begin_index + len(timesteps)]:
                 raise ValueError(f"{type(self.scheduler).__name__}: timesteps must be the scheduler's own, from step "
                                  f"index begin_index on")
-        if kind in ANCESTRAL and noise_seed is None:
-            raise ValueError(f"the {kind} sampler draws noise on the device: pass noise_seed")
-        if kind == "pndm":
-            check_pndm_start(begin_index, known is not None)
+        if update == "ancestral" and noise_seed is None:
+            raise ValueError(f"{type(self.scheduler).__name__}: an ancestral sampler draws noise on the device: pass "
+                             f"noise_seed")
+        _, coefs = self.scheduler.loop_steps(timesteps, begin_index, eta, init=known is not None)
         unet, dc, dev = self.denoising_unet, self.dist, latents.device
         _, C, F, H, W = latents.shape
         hw = H * W
@@ -541,7 +517,7 @@ class VExpressPipeline:
                             nW, C, f, hw, dev, apg=apg)
         self.last_schedule, self.last_guidance = guidance.schedule, guidance.report
         preds = torch.empty((nW, C, f, hw), device=dev, dtype=torch.float32)
-        sampler = Sampler(self.scheduler, kind, latents, timesteps, begin_index, eta, noise_seed)
+        sampler = Sampler(self.scheduler, update, coefs, latents, begin_index, noise_seed)
         known = Known(self.scheduler, init, noise, kmask, len(timesteps), begin_index)
         self.last_init = known.report
         if known.active:
@@ -634,8 +610,7 @@ class VExpressPipeline:
         `latents` / `generator` give the N(0,1) noise, as without an init clip."""
         # an unsupported scheduler, eta with one other than DDIM, guidance controls out of range or init-video arguments
         # that do not fit the clip fail here, before the prologue
-        kind = self._sampler(eta)
-        ancestral = kind in ANCESTRAL
+        ancestral = self._sampler(eta) == "ancestral"
         check_guidance(guidance_rescale, guidance_start, guidance_end, max(int(num_inference_steps), 1))
         audio_guidance_scale = check_audio_guidance(audio_guidance_scale)
         apg = check_apg((apg_eta, apg_norm_threshold, apg_momentum), guidance_rescale)
@@ -665,11 +640,9 @@ class VExpressPipeline:
         self.scheduler.set_timesteps(num_inference_steps)
         init_t = min(int(num_inference_steps * strength), num_inference_steps)
         begin_index = max(num_inference_steps - init_t, 0)
-        if kind == "pndm":
-            check_pndm_start(begin_index, init_video is not None or init_latents is not None)
         timesteps = self.scheduler.timesteps[begin_index:].tolist()
-        if ancestral:
-            ancestral_coefficients(self.scheduler, kind, timesteps, begin_index, eta)   # e.g. eta too large: ValueError here
+        # a start the scheduler does not build, coefficients it cannot form (e.g. eta too large: ValueError) fail here
+        self.scheduler.loop_steps(timesteps, begin_index, eta, init=init_video is not None or init_latents is not None)
         writer = ReferenceAttentionControl(self.reference_net, do_classifier_free_guidance=do_cfg, mode="write",
                                            batch_size=1, fusion_blocks="full")
         reader = ReferenceAttentionControl(self.denoising_unet, do_classifier_free_guidance=do_cfg, mode="read",

@@ -3,8 +3,9 @@ buffers and host-side coefficients, so that a timestep reads straight down:
     UNet calls of guidance.plan(i) -> all_gather_units -> guidance.combine -> stitch.reduce -> sampler.update -> known.after
   Stitch    how the window predictions of a step become one prediction per frame: the mean plan, or the weighted pre-pass;
   Guidance  which rows a step runs per window and the one launch that combines them (rescaled or not);
-  Sampler   the update of the scheduler in use, its per-step coefficients and, for the sigma (VE) schedulers - Euler
-            ancestral, Euler, LMS - the VE <-> VP frame;
+  Sampler   the update and the per-step coefficients the scheduler in use names (scheduler.loop_steps), that update's
+            buffers and, for a scheduler that has `frame_scale` - the sigma (VE) ones: Euler ancestral, Euler, LMS - the
+            VE <-> VP frame;
   Known     the known region of init-video sampling: the start latents and the blend after every step.
 A choice that does not depend on the timestep is made in a constructor (a method bound there), never in the loop.  Every
 kernel wrapper is looked up as `ops.<name>` when it is called: tests and tools replace them there."""
@@ -13,12 +14,6 @@ from typing import Any, List, NamedTuple
 import torch
 
 from . import ops
-
-# the samplers that draw noise at every step (vx_overlap_ancestral_step)
-ANCESTRAL = ("ddim-eta", "euler-a")
-# the linear multistep samplers (vx_overlap_linear_step), and the samplers whose scheduler works in the VE frame
-LINEAR = ("euler", "lms", "pndm")
-VE_FRAME = ("euler-a", "euler", "lms")
 
 # The batch rows a window can run, as (bank row, keypoint row, audio row) of the CFG-layout conditioning (row 0 zeros,
 # row 1 real): "u" drops everything, "m" ("silent") keeps the reference bank and the keypoints and drops the audio, "c"
@@ -41,13 +36,6 @@ class UnitCall(NamedTuple):
     shard: Any
     s0: int
     n_slots: int
-
-
-def ancestral_coefficients(scheduler, kind, timesteps, begin_index, eta):
-    """Per-step (alpha_s, sigma_s, c_x, c_0, c_z) of an ancestral sampler, resolved on the host before the loop."""
-    if kind == "ddim-eta":
-        return [scheduler.ancestral_coefficients(t, eta) for t in timesteps]
-    return [scheduler.ancestral_coefficients(begin_index + i) for i in range(len(timesteps))]
 
 
 class Stitch:
@@ -165,36 +153,28 @@ class Guidance:
 
 
 class Sampler:
-    """The update of one frame set per timestep: "ddim" (vx_overlap_ddim_step), "dpm" (vx_overlap_multistep_step, with the
-    previous step's x0 of every frame in `x0_hist`: identical on every rank, like the latents), an ancestral one
-    (vx_overlap_ancestral_step, noise keyed by `noise_seed` and the step index) or a linear multistep one - "euler", "lms",
-    "pndm" (vx_overlap_linear_step, with `history`, three per-frame slots, and `saved`, PNDM's saved sample: allocated
-    only when some step names them, never read before they are written, identical on every rank).  The coefficients of
-    every step are resolved on the host here.  Euler ancestral, Euler, LMS: the latents come and go in the scheduler's
-    (VE) frame and the loop runs in the VP frame x / sqrt(1 + sigma^2); `frame_scale` is the scheduler's, None for the
-    others."""
+    """The update of one frame set per timestep, `update` and `coefs` as the scheduler's loop_steps returned them: "ddim"
+    (vx_overlap_ddim_step), "multistep" (vx_overlap_multistep_step, with the previous step's x0 of every frame in
+    `x0_hist`: identical on every rank, like the latents), "ancestral" (vx_overlap_ancestral_step, noise keyed by
+    `noise_seed` and the step index) or "linear" (vx_overlap_linear_step, with `history`, three per-frame slots, and
+    `saved`, PNDM's saved sample: allocated only when some step names them, never read before they are written, identical
+    on every rank).  A scheduler that has `frame_scale` (Euler ancestral, Euler, LMS): the latents come and go in its
+    (VE) frame and the loop runs in the VP frame x / sqrt(1 + sigma^2); None for the others."""
 
-    def __init__(self, scheduler, kind, latents, timesteps, begin_index, eta, noise_seed):
-        self.begin_index, self.steps = begin_index, len(timesteps)
-        self.frame_scale = scheduler.frame_scale if kind in VE_FRAME and timesteps else None
-        if kind in LINEAR:
-            self.coefs = [scheduler.linear_coefficients(begin_index + i, begin_index) for i in range(self.steps)]
-            slots = any(max(cf[:4]) >= 0 for cf in self.coefs)
+    def __init__(self, scheduler, update, coefs, latents, begin_index, noise_seed):
+        self.begin_index, self.steps, self.coefs = begin_index, len(coefs), coefs
+        self.frame_scale = getattr(scheduler, "frame_scale", None) if coefs else None
+        if update == "multistep":
+            self.x0_hist = torch.empty_like(latents)
+        elif update == "ancestral":
+            self.noise_seed = int(noise_seed)
+        elif update == "linear":
+            slots = any(max(cf[:4]) >= 0 for cf in coefs)
             self.history = torch.empty((3,) + tuple(latents.shape[1:]), device=latents.device,
                                        dtype=torch.float32) if slots else None
-            self.saved = torch.empty_like(latents) if any(cf.saved_mode for cf in self.coefs) else None
-            self._update = self._linear
-        elif kind == "dpm":
-            self.x0_hist = torch.empty_like(latents)
-            self.coefs = [scheduler.multistep_coefficients(begin_index + i, begin_index) for i in range(self.steps)]
-            self._update = self._multistep
-        elif kind in ANCESTRAL:
-            self.coefs = ancestral_coefficients(scheduler, kind, timesteps, begin_index, eta)
-            self.noise_seed = int(noise_seed)
-            self._update = self._ancestral
-        else:
-            self.coefs = [scheduler.step_coefficients(int(t)) for t in timesteps]
-            self._update = self._ddim
+            self.saved = torch.empty_like(latents) if any(cf.saved_mode for cf in coefs) else None
+        self._update = {"ddim": self._ddim, "multistep": self._multistep, "ancestral": self._ancestral,
+                        "linear": self._linear}[update]
 
     def start(self, latents):
         if self.frame_scale is not None:

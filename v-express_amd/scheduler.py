@@ -11,6 +11,13 @@ eta > 0 through `DDIMScheduler.ancestral_coefficients(t, eta)`, EulerAncestralDi
 `ancestral_coefficients(i)`) feed `vx_overlap_ancestral_step`, which draws its noise on the device.  The rest of the
 reference's list - EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler - are linear multistep updates in the loop's
 frame and feed `vx_overlap_linear_step` through `linear_coefficients(i, begin_index)`.
+
+What the classes share is stated once: `_Scheduler` (all six) holds `from_config`, the refusal of options that are not
+built, the beta / alphas_cumprod / sigma tables, the timestep -> step index lookup and the index checks, and the
+contract with the denoising loop, `loop_steps(timesteps, begin_index, eta, init)` -> (update, coefs): which of the four
+fused updates ("ddim", "multistep", "ancestral", "linear") the scheduler runs, the per-step coefficients that update
+takes, and every rule about eta or the start of a run that depends on the class.  `_AlphaScheduler` (DDIM, PNDM) adds the
+noise levels read from alphas_cumprod, `_SigmaScheduler` (Euler ancestral, Euler, LMS) the sigma (VE) parametrisation.
 """
 from types import SimpleNamespace
 
@@ -52,34 +59,126 @@ def _timestep_list(timesteps):
     return [float(timesteps)]
 
 
-class DDIMScheduler:
-    order = 1
+def _trailing(num_train_timesteps, n, dtype):
+    """diffusers' "trailing" timestep spacing: n timesteps from num_train_timesteps - 1 down, as a numpy array."""
+    return np.round(np.arange(num_train_timesteps, 0, -num_train_timesteps / n)).astype(dtype) - 1
 
+
+def _vp(sigma):
+    """(a, s) = (1, sigma) / sqrt(1 + sigma^2) in float64: the variance-preserving pair of a sigma."""
+    a = 1.0 / math.sqrt(sigma * sigma + 1.0)
+    return a, sigma * a
+
+
+class _Scheduler:
+    """What all six schedulers share; a subclass sets `config` and then calls `_tables`."""
+    order = 1
+    init_noise_sigma = 1.0
+
+    @classmethod
+    def from_config(cls, cfg, **overrides):
+        """From a dict or another scheduler's `config` (e.g. `DDIMScheduler(...).config`)."""
+        cfg = dict(cfg) if isinstance(cfg, dict) else dict(vars(cfg))
+        cfg.update(overrides)
+        return cls(**cfg)
+
+    def _check_options(self, *options):
+        """`options`: (name, value, accepted) triples of the class's own table."""
+        for name, value, ok in options:
+            if not ok:
+                raise NotImplementedError(f"{type(self).__name__}: {name}={value!r} is not built")
+
+    def _tables(self, sigma):
+        """betas and alphas_cumprod of `config`, float32; with `sigma` the sigma table too, else final_alpha_cumprod."""
+        cfg = self.config
+        self.betas = _betas(cfg.num_train_timesteps, cfg.beta_start, cfg.beta_end, cfg.beta_schedule,
+                            cfg.rescale_betas_zero_snr)
+        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, 0)
+        self.num_inference_steps = None
+        if not sigma:
+            self.final_alpha_cumprod = torch.tensor(1.0) if cfg.set_alpha_to_one else self.alphas_cumprod[0]
+            return
+        if cfg.rescale_betas_zero_snr:
+            # the zero-SNR table ends at alphas_cumprod = 0: diffusers clamps it so that the first sigma is finite (4096)
+            self.alphas_cumprod[-1] = 2 ** -24
+        # sigma(t) = sqrt((1 - abar_t) / abar_t) in float32, as diffusers computes it
+        self.sigma_table = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def _index_of(self, timestep, repeated=False):
+        """Step index of a schedule timestep: the first match (diffusers' index_for_timestep) or, with `repeated`, the
+        second one of a timestep the list holds twice (diffusers' _init_step_index)."""
+        t = float(timestep)
+        hits = [i for i, own in enumerate(self.timesteps.tolist()) if float(own) == t]
+        if not hits:
+            raise ValueError(f"timestep {t} is not in this schedule")
+        return hits[1 if repeated and len(hits) > 1 else 0]
+
+    def _check_index(self, i, begin_index=0, closed=False, n=None):
+        if self.num_inference_steps is None:
+            raise RuntimeError("call set_timesteps() first")
+        n = self.num_inference_steps if n is None else n
+        if not begin_index <= i < n + (1 if closed else 0):
+            raise IndexError(f"step index {i} outside [{begin_index}, {n}{']' if closed else ')'}")
+
+    def loop_steps(self, timesteps, begin_index, eta=0.0, init=False):
+        """What the denoising loop runs for `timesteps`, the scheduler's own from step index `begin_index` on:
+        (update, coefs) - the fused update, one of "ddim", "multistep", "ancestral", "linear" (ops.overlap_<update>_step),
+        and the list of per-step coefficients that update takes.  `init`: the run starts from a noised clip.  Everything
+        the class does not build fails here: eta is DDIM's option, NotImplementedError from every other class."""
+        raise NotImplementedError
+
+    def _no_eta(self, eta):
+        if eta != 0.0:
+            raise NotImplementedError(f"eta != 0 is a DDIM option; {type(self).__name__} does not take it")
+
+
+class _AlphaScheduler(_Scheduler):
+    """DDIM and PNDM: the noise level of a timestep is read from alphas_cumprod (unclamped: both updates are finite at
+    abar = 0), and of the state after the last step from final_alpha_cumprod."""
+
+    def noise_coefficients(self, j):
+        """(a_j, s_j) = (sqrt(abar), sqrt(1 - abar)) of timesteps[j], the level the latents have at step index j;
+        j = len(timesteps): the level after the last step (final_alpha_cumprod).  Float64 arithmetic on the float32
+        table: x_j = a_j x0 + s_j noise is `add_noise(x0, noise, timesteps[j])`."""
+        n = len(self.timesteps)
+        if not 0 <= j <= n:
+            raise IndexError(f"step index {j} outside [0, {n}]")
+        abar = float(self.alphas_cumprod[int(self.timesteps[j])]) if j < n else float(self.final_alpha_cumprod)
+        return math.sqrt(abar), math.sqrt(1.0 - abar)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' add_noise: sqrt(abar_t) x0 + sqrt(1 - abar_t) noise, t one timestep or one per sample of the
+        batch (host torch arithmetic; the loop forms its start latents with vx_known_blend)."""
+        abar = [float(self.alphas_cumprod[int(t)]) for t in _timestep_list(timesteps)]
+        a = _per_sample([math.sqrt(v) for v in abar], original_samples)
+        s = _per_sample([math.sqrt(1.0 - v) for v in abar], original_samples)
+        return a * original_samples + s * noise
+
+
+class DDIMScheduler(_AlphaScheduler):
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                  clip_sample=True, set_alpha_to_one=True, steps_offset=0, prediction_type="epsilon",
                  timestep_spacing="leading", rescale_betas_zero_snr=False, **unused):
-        betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
-        self.betas = betas
-        self.alphas_cumprod = torch.cumprod(1.0 - betas, 0)
-        self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, clip_sample=clip_sample,
                                       steps_offset=steps_offset, prediction_type=prediction_type,
                                       timestep_spacing=timestep_spacing, beta_start=beta_start, beta_end=beta_end,
                                       beta_schedule=beta_schedule, set_alpha_to_one=set_alpha_to_one,
                                       rescale_betas_zero_snr=rescale_betas_zero_snr)
+        self._tables(sigma=False)
         if clip_sample:
             raise NotImplementedError("clip_sample=True is not used by V-Express (inference_v2.yaml:28)")
         if prediction_type != "v_prediction":
             raise NotImplementedError("only v_prediction (inference_v2.yaml:31) is built")
-        self.init_noise_sigma = 1.0
-        self.num_inference_steps = None
         self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1)
 
     def set_timesteps(self, num_inference_steps, device=None):
         T, sp = self.config.num_train_timesteps, self.config.timestep_spacing
         self.num_inference_steps = num_inference_steps
         if sp == "trailing":
-            ts = np.round(np.arange(T, 0, -T / num_inference_steps)).astype(np.int64) - 1
+            ts = _trailing(T, num_inference_steps, np.int64)
         elif sp == "leading":
             ts = (np.arange(0, num_inference_steps) * (T // num_inference_steps)).round()[::-1].astype(np.int64)
             ts = ts + self.config.steps_offset
@@ -88,9 +187,6 @@ class DDIMScheduler:
         else:
             raise ValueError(sp)
         self.timesteps = torch.from_numpy(ts.copy())
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
 
     def _alphas(self, t):
         t = int(t)
@@ -122,23 +218,14 @@ class DDIMScheduler:
         sa, s1a = math.sqrt(a), math.sqrt(1.0 - a)
         return sa, s1a, k / s1a, -(math.sqrt(ap) - k * sa / s1a), sig
 
-    def noise_coefficients(self, j):
-        """(a_j, s_j) = (sqrt(abar), sqrt(1 - abar)) of timesteps[j], the level the latents have at step index j;
-        j = len(timesteps): the level after the last step (final_alpha_cumprod).  Float64 arithmetic on the float32
-        table: x_j = a_j x0 + s_j noise is `add_noise(x0, noise, timesteps[j])`."""
-        n = len(self.timesteps)
-        if not 0 <= j <= n:
-            raise IndexError(f"step index {j} outside [0, {n}]")
-        abar = float(self.alphas_cumprod[int(self.timesteps[j])]) if j < n else float(self.final_alpha_cumprod)
-        return math.sqrt(abar), math.sqrt(1.0 - abar)
-
-    def add_noise(self, original_samples, noise, timesteps):
-        """diffusers' DDIMScheduler.add_noise: sqrt(abar_t) x0 + sqrt(1 - abar_t) noise, t one timestep or one per
-        sample of the batch (host torch arithmetic; the loop forms its start latents with vx_known_blend)."""
-        abar = [float(self.alphas_cumprod[int(t)]) for t in _timestep_list(timesteps)]
-        a = _per_sample([math.sqrt(v) for v in abar], original_samples)
-        s = _per_sample([math.sqrt(1.0 - v) for v in abar], original_samples)
-        return a * original_samples + s * noise
+    def loop_steps(self, timesteps, begin_index, eta=0.0, init=False):
+        """ "ddim" with `step_coefficients` for eta = 0, "ancestral" with `ancestral_coefficients` for eta > 0 (ValueError
+        for eta < 0 or too large); both read the timesteps themselves, `begin_index` only numbers the noise draws."""
+        if eta < 0:
+            raise ValueError(f"eta must be >= 0, got {eta}")
+        if eta == 0.0:
+            return "ddim", [self.step_coefficients(int(t)) for t in timesteps]
+        return "ancestral", [self.ancestral_coefficients(t, eta) for t in timesteps]
 
     def step(self, model_output, timestep, sample, eta=0.0, **unused):
         if eta != 0.0:
@@ -149,7 +236,7 @@ class DDIMScheduler:
         return SimpleNamespace(prev_sample=sap * x0 + s1ap * eps, pred_original_sample=x0)
 
 
-class DPMSolverMultistepScheduler:
+class DPMSolverMultistepScheduler(_Scheduler):
     """DPM-Solver++ (multistep, data prediction, midpoint) for the zero-terminal-SNR v-prediction schedule: the arithmetic
     of diffusers==0.29.2 `DPMSolverMultistepScheduler` restated for the options listed in `__init__` (any other value
     raises NotImplementedError naming the option).
@@ -158,7 +245,6 @@ class DPMSolverMultistepScheduler:
         x0 = alpha_i x - sigma_i v ;   x' = c_x x - c_0 x0 + c_1 x0_prev
     with the previous step's x0 kept on the device.  `step()` is the stateful diffusers-style tensor API.
     """
-    order = 1
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                  trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False,
@@ -169,25 +255,18 @@ class DPMSolverMultistepScheduler:
                  **unused):
         # (clip_sample, set_alpha_to_one, ... of a DDIM configuration are not parameters of this solver: ignored, as
         # diffusers' from_config does)
-        for name, value, ok in (("trained_betas", trained_betas, trained_betas is None),
-                                ("solver_order", solver_order, solver_order in (1, 2)),
-                                ("prediction_type", prediction_type, prediction_type == "v_prediction"),
-                                ("thresholding", thresholding, not thresholding),
-                                ("algorithm_type", algorithm_type, algorithm_type == "dpmsolver++"),
-                                ("solver_type", solver_type, solver_type == "midpoint"),
-                                ("use_karras_sigmas", use_karras_sigmas, not use_karras_sigmas),
-                                ("use_lu_lambdas", use_lu_lambdas, not use_lu_lambdas),
-                                ("final_sigmas_type", final_sigmas_type, final_sigmas_type in ("zero", "sigma_min")),
-                                ("lambda_min_clipped", lambda_min_clipped, lambda_min_clipped == -float("inf")),
-                                ("variance_type", variance_type, variance_type is None),
-                                ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing")):
-            if not ok:
-                raise NotImplementedError(f"DPMSolverMultistepScheduler: {name}={value!r} is not built")
-        self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
-        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, 0)
-        if rescale_betas_zero_snr:
-            # the zero-SNR table ends at alphas_cumprod = 0: diffusers clamps it so that the first sigma is finite
-            self.alphas_cumprod[-1] = 2 ** -24
+        self._check_options(("trained_betas", trained_betas, trained_betas is None),
+                            ("solver_order", solver_order, solver_order in (1, 2)),
+                            ("prediction_type", prediction_type, prediction_type == "v_prediction"),
+                            ("thresholding", thresholding, not thresholding),
+                            ("algorithm_type", algorithm_type, algorithm_type == "dpmsolver++"),
+                            ("solver_type", solver_type, solver_type == "midpoint"),
+                            ("use_karras_sigmas", use_karras_sigmas, not use_karras_sigmas),
+                            ("use_lu_lambdas", use_lu_lambdas, not use_lu_lambdas),
+                            ("final_sigmas_type", final_sigmas_type, final_sigmas_type in ("zero", "sigma_min")),
+                            ("lambda_min_clipped", lambda_min_clipped, lambda_min_clipped == -float("inf")),
+                            ("variance_type", variance_type, variance_type is None),
+                            ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing"))
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                                       beta_schedule=beta_schedule, solver_order=solver_order,
                                       prediction_type=prediction_type, algorithm_type=algorithm_type,
@@ -195,20 +274,10 @@ class DPMSolverMultistepScheduler:
                                       euler_at_final=euler_at_final, final_sigmas_type=final_sigmas_type,
                                       timestep_spacing=timestep_spacing, steps_offset=steps_offset,
                                       rescale_betas_zero_snr=rescale_betas_zero_snr)
-        # sigma(t) = sqrt((1 - abar_t) / abar_t) in float32, as diffusers computes it
-        self.sigma_table = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
-        self.init_noise_sigma = 1.0
-        self.num_inference_steps = None
+        self._tables(sigma=True)
         self.timesteps = None
         self.sigmas = None
         self._reset()
-
-    @classmethod
-    def from_config(cls, cfg, **overrides):
-        """From a dict or another scheduler's `config` (e.g. `DDIMScheduler(...).config`)."""
-        cfg = dict(cfg) if isinstance(cfg, dict) else dict(vars(cfg))
-        cfg.update(overrides)
-        return cls(**cfg)
 
     def _reset(self):
         self.step_index = None
@@ -218,26 +287,19 @@ class DPMSolverMultistepScheduler:
     def set_timesteps(self, num_inference_steps, device=None):
         T = self.config.num_train_timesteps
         self.num_inference_steps = num_inference_steps
-        ts = np.round(np.arange(T, 0, -T / num_inference_steps)).astype(np.int64) - 1
-        self.timesteps = torch.from_numpy(ts.copy())
+        self.timesteps = torch.from_numpy(_trailing(T, num_inference_steps, np.int64))
         sig = self.sigma_table[self.timesteps]
         last = torch.zeros(1) if self.config.final_sigmas_type == "zero" else self.sigma_table[:1]
         self.sigmas = torch.cat([sig, last]).to(torch.float32)
         self._reset()
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
 
     def solver_order_at(self, i, begin_index=0):
         """Order of the update at step index i of a run that started at `begin_index` (diffusers' step(): first order
         at the first step of a run, at solver_order 1, and at the last step under final_sigmas_type "zero",
         euler_at_final, or lower_order_final below 15 steps).  diffusers' other small-n rule, `lower_order_second` at
         i = n - 2, caps the order at 2 and so changes nothing for solver_order <= 2."""
+        self._check_index(i, begin_index)
         cfg, n = self.config, self.num_inference_steps
-        if n is None:
-            raise RuntimeError("call set_timesteps() first")
-        if not begin_index <= i < n:
-            raise IndexError(f"step index {i} outside [{begin_index}, {n})")
         last = i == n - 1 and (cfg.euler_at_final or (cfg.lower_order_final and n < 15)
                                or cfg.final_sigmas_type == "zero")
         return 1 if (cfg.solver_order == 1 or i == begin_index or last) else 2
@@ -248,47 +310,33 @@ class DPMSolverMultistepScheduler:
         c_0 = -1, c_1 = 0), so no inf or NaN reaches the kernel."""
         order = self.solver_order_at(i, begin_index)
         sg = [float(s) for s in self.sigmas]
-
-        def alpha(s):
-            return 1.0 / math.sqrt(s * s + 1.0)
         s0, s1 = sg[i], sg[i + 1]
-        a_i, sd_i = alpha(s0), s0 * alpha(s0)
+        (a_i, sd_i), (a_1, sd_1) = _vp(s0), _vp(s1)
         if s1 == 0.0:
             return a_i, sd_i, 0.0, -1.0, 0.0
         h = math.log(s0) - math.log(s1)                                    # lambda = -log sigma
-        A = alpha(s1) * math.expm1(-h)
-        c_x = (s1 * alpha(s1)) / sd_i
+        A = a_1 * math.expm1(-h)
+        c_x = sd_1 / sd_i
         B = 0.0
         if order == 2:
             r = (math.log(sg[i - 1]) - math.log(s0)) / h
             B = 0.5 * A / r
         return a_i, sd_i, c_x, A + B, B
 
-    def _indices_of(self, timesteps):
-        """Step indices of schedule timesteps (diffusers' index_for_timestep: the first match)."""
-        own = [float(t) for t in self.timesteps.tolist()]
-        out = []
-        for t in _timestep_list(timesteps):
-            if t not in own:
-                raise ValueError(f"timestep {t} is not in this schedule")
-            out.append(own.index(t))
-        return out
+    def loop_steps(self, timesteps, begin_index, eta=0.0, init=False):
+        self._no_eta(eta)
+        return "multistep", [self.multistep_coefficients(begin_index + i, begin_index) for i in range(len(timesteps))]
 
     def noise_coefficients(self, j):
         """(a_j, s_j) = (alpha_t, sigma_t) of sigmas[j], the level the latents have at step index j (j = number of
         steps: the final sigma).  Float64 arithmetic on the float32 sigmas."""
-        if self.sigmas is None or self.num_inference_steps is None:
-            raise RuntimeError("call set_timesteps() first")
-        if not 0 <= j <= self.num_inference_steps:
-            raise IndexError(f"step index {j} outside [0, {self.num_inference_steps}]")
-        sg = float(self.sigmas[j])
-        a = 1.0 / math.sqrt(sg * sg + 1.0)
-        return a, sg * a
+        self._check_index(j, closed=True)
+        return _vp(float(self.sigmas[j]))
 
     def add_noise(self, original_samples, noise, timesteps):
         """diffusers' DPMSolverMultistepScheduler.add_noise: alpha_t x0 + sigma_t noise at the schedule's own timesteps
         (one, or one per sample of the batch)."""
-        pairs = [self.noise_coefficients(i) for i in self._indices_of(timesteps)]
+        pairs = [self.noise_coefficients(self._index_of(t)) for t in _timestep_list(timesteps)]
         a = _per_sample([p[0] for p in pairs], original_samples)
         s = _per_sample([p[1] for p in pairs], original_samples)
         return a * original_samples + s * noise
@@ -296,10 +344,7 @@ class DPMSolverMultistepScheduler:
     def step(self, model_output, timestep, sample, return_dict=True, **unused):
         """One update on tensors (v-prediction `model_output`), keeping the step index and the last x0 like diffusers."""
         if self.step_index is None:
-            hits = (self.timesteps == int(timestep)).nonzero()
-            if len(hits) == 0:
-                raise ValueError(f"timestep {int(timestep)} is not in this schedule")
-            self.step_index = int(hits[0])
+            self.step_index = self._index_of(int(timestep))
         i = self.step_index
         a_i, sd_i, c_x, c_0, c_1 = self.multistep_coefficients(i, begin_index=i - self._taken)
         x0 = a_i * sample - sd_i * model_output
@@ -313,54 +358,23 @@ class DPMSolverMultistepScheduler:
         return out if return_dict else (prev,)
 
 
-class EulerAncestralDiscreteScheduler:
-    """Euler ancestral sampling for the zero-terminal-SNR v-prediction schedule: the arithmetic of diffusers==0.29.2
-    `EulerAncestralDiscreteScheduler` restated for the options listed in `__init__` (any other value raises
-    NotImplementedError naming the option).
+class _SigmaScheduler(_Scheduler):
+    """What the three samplers of the sigma (VE) parametrisation - Euler ancestral, Euler, LMS - share: the clamped
+    zero-SNR table, sigmas = table[timesteps] + [0], init_noise_sigma = the largest sigma, the UNet input
+    x / sqrt(1 + sigma^2), and the VP pair and frame scale the loop asks for.  A class that has `frame_scale` hands its
+    latents over in the VE frame; the loop runs in the VP frame."""
 
-    diffusers works in the VE frame (x_ve = x0 + sigma eps, `scale_model_input` divides by sqrt(1 + sigma^2)).  The loop
-    runs in the VP frame x_vp = x_ve / sqrt(1 + sigma^2) - exactly the UNet input - with the update of the fused
-    `vx_overlap_ancestral_step` kernel, fed by `ancestral_coefficients(i)`:
-        x0 = alpha_s x - sigma_s v ;   x' = c_x x - c_0 x0 + c_z z
-    `step()` is the stateful diffusers-style tensor API in the VE frame.
-    """
-    order = 1
-
-    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
-                 trained_betas=None, prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0,
-                 rescale_betas_zero_snr=False, **unused):
-        # (clip_sample, set_alpha_to_one, ... of a DDIM configuration are not parameters of this sampler: ignored, as
-        # diffusers' from_config does)
-        for name, value, ok in (("trained_betas", trained_betas, trained_betas is None),
-                                ("beta_schedule", beta_schedule, beta_schedule == "scaled_linear"),
-                                ("prediction_type", prediction_type, prediction_type == "v_prediction"),
-                                ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing")):
-            if not ok:
-                raise NotImplementedError(f"EulerAncestralDiscreteScheduler: {name}={value!r} is not built")
-        self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
-        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, 0)
-        if rescale_betas_zero_snr:
-            # the zero-SNR table ends at alphas_cumprod = 0: diffusers clamps it so that the first sigma is finite
-            self.alphas_cumprod[-1] = 2 ** -24
-        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
-                                      beta_schedule=beta_schedule, prediction_type=prediction_type,
-                                      timestep_spacing=timestep_spacing, steps_offset=steps_offset,
-                                      rescale_betas_zero_snr=rescale_betas_zero_snr)
-        # sigma(t) = sqrt((1 - abar_t) / abar_t) in float32, as diffusers computes it
-        self.sigma_table = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
+    def _sigma_tables(self):
+        self._tables(sigma=True)
+        T = self.config.num_train_timesteps
         self.sigmas = torch.cat([self.sigma_table.flip(0), torch.zeros(1)]).to(torch.float32)
-        self.timesteps = torch.linspace(0, num_train_timesteps - 1, num_train_timesteps,
-                                        dtype=torch.float64).flip(0).to(torch.float32)
-        self.num_inference_steps = None
+        self.timesteps = torch.linspace(0, T - 1, T, dtype=torch.float64).flip(0).to(torch.float32)
+        self._reset()
+
+    def _reset(self):
         self._step_index = None
         self._begin_index = None
-
-    @classmethod
-    def from_config(cls, cfg, **overrides):
-        """From a dict or another scheduler's `config` (e.g. `DDIMScheduler(...).config`)."""
-        cfg = dict(cfg) if isinstance(cfg, dict) else dict(vars(cfg))
-        cfg.update(overrides)
-        return cls(**cfg)
+        self._derivatives = []
 
     @property
     def init_noise_sigma(self):
@@ -381,21 +395,16 @@ class EulerAncestralDiscreteScheduler:
     def set_timesteps(self, num_inference_steps, device=None):
         T = self.config.num_train_timesteps
         self.num_inference_steps = num_inference_steps
-        ts = np.arange(T, 0, -T / num_inference_steps).round().astype(np.float32) - 1
-        self.timesteps = torch.from_numpy(ts.copy())
+        self.timesteps = torch.from_numpy(_trailing(T, num_inference_steps, np.float32))
         sig = self.sigma_table[self.timesteps.long()]
         self.sigmas = torch.cat([sig, torch.zeros(1)]).to(torch.float32)
-        self._step_index = None
-        self._begin_index = None
+        self._reset()
 
     def _init_step_index(self, timestep):
-        if self._begin_index is not None:
+        if self._begin_index is None:
+            self._step_index = self._index_of(timestep, repeated=True)
+        else:
             self._step_index = self._begin_index
-            return
-        hits = (self.timesteps == float(timestep)).nonzero()
-        if len(hits) == 0:
-            raise ValueError(f"timestep {float(timestep)} is not in this schedule")
-        self._step_index = int(hits[1 if len(hits) > 1 else 0])
 
     def scale_model_input(self, sample, timestep=None):
         """x_ve -> x_vp = x_ve / sqrt(1 + sigma^2) at the current step (diffusers' scaling of the UNet input)."""
@@ -404,15 +413,70 @@ class EulerAncestralDiscreteScheduler:
         sigma = self.sigmas[self._step_index]
         return sample / ((sigma ** 2 + 1) ** 0.5)
 
+    def _vp_at(self, j):
+        return _vp(float(self.sigmas[j]))
+
+    def loop_steps(self, timesteps, begin_index, eta=0.0, init=False):
+        """The two deterministic samplers (Euler ancestral has its own)."""
+        self._no_eta(eta)
+        return "linear", [self.linear_coefficients(begin_index + i, begin_index) for i in range(len(timesteps))]
+
+    def noise_coefficients(self, j):
+        """(a_j, s_j) = (1, sigma_j) / sqrt(1 + sigma_j^2) of sigmas[j]: the variance-preserving pair of the frame the
+        loop runs in (x_vp = x_ve / sqrt(1 + sigma^2)); j = number of steps: the final sigma = 0, (1, 0)."""
+        self._check_index(j, closed=True)
+        return self._vp_at(j)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' add_noise in the scheduler's own (VE) frame: x0 + sigma noise at the schedule's own timesteps (one,
+        or one per sample of the batch)."""
+        sig = [float(self.sigmas[self._index_of(t)]) for t in _timestep_list(timesteps)]
+        return original_samples + _per_sample(sig, original_samples) * noise
+
+    def frame_scale(self, i):
+        """sqrt(1 + sigmas[i]^2): x_ve = frame_scale(i) x_vp at step index i (1 at the final sigma = 0)."""
+        s = float(self.sigmas[i])
+        return math.sqrt(1.0 + s * s)
+
+    def _derivative(self, model_output, sample, i):
+        """diffusers' v-prediction arithmetic in the VE frame: (x0, d = (x - x0) / sigma = eps), float64 scalars."""
+        sigma = float(self.sigmas[i])
+        x0 = model_output * (-sigma / math.sqrt(sigma * sigma + 1.0)) + sample / (sigma * sigma + 1.0)
+        return x0, (sample - x0) / sigma
+
+
+class EulerAncestralDiscreteScheduler(_SigmaScheduler):
+    """Euler ancestral sampling for the zero-terminal-SNR v-prediction schedule: the arithmetic of diffusers==0.29.2
+    `EulerAncestralDiscreteScheduler` restated for the options listed in `__init__` (any other value raises
+    NotImplementedError naming the option).
+
+    diffusers works in the VE frame (x_ve = x0 + sigma eps, `scale_model_input` divides by sqrt(1 + sigma^2)).  The loop
+    runs in the VP frame x_vp = x_ve / sqrt(1 + sigma^2) - exactly the UNet input - with the update of the fused
+    `vx_overlap_ancestral_step` kernel, fed by `ancestral_coefficients(i)`:
+        x0 = alpha_s x - sigma_s v ;   x' = c_x x - c_0 x0 + c_z z
+    `step()` is the stateful diffusers-style tensor API in the VE frame.
+    """
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 trained_betas=None, prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0,
+                 rescale_betas_zero_snr=False, **unused):
+        # (clip_sample, set_alpha_to_one, ... of a DDIM configuration are not parameters of this sampler: ignored, as
+        # diffusers' from_config does)
+        self._check_options(("trained_betas", trained_betas, trained_betas is None),
+                            ("beta_schedule", beta_schedule, beta_schedule == "scaled_linear"),
+                            ("prediction_type", prediction_type, prediction_type == "v_prediction"),
+                            ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing"))
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, prediction_type=prediction_type,
+                                      timestep_spacing=timestep_spacing, steps_offset=steps_offset,
+                                      rescale_betas_zero_snr=rescale_betas_zero_snr)
+        self._sigma_tables()
+
     def ancestral_coefficients(self, i):
         """(alpha_s, sigma_s, c_x, c_0, c_z) of step index i in the VP frame: x0 = alpha_s x - sigma_s v,
         x' = c_x x - c_0 x0 + c_z z with x, x' = x_ve / sqrt(1 + sigma^2) at sigmas[i], sigmas[i + 1].  Float64
         arithmetic on the float32 sigmas; a step that ends at sigma = 0 returns x0 exactly (c_x = 0, c_0 = -1, c_z = 0)."""
-        n = self.num_inference_steps
-        if n is None:
-            raise RuntimeError("call set_timesteps() first")
-        if not 0 <= i < n:
-            raise IndexError(f"step index {i} outside [0, {n})")
+        self._check_index(i)
         s, s1 = float(self.sigmas[i]), float(self.sigmas[i + 1])
         r = math.sqrt(1.0 + s * s)
         alpha_s, sigma_s = 1.0 / r, s / r
@@ -423,33 +487,9 @@ class EulerAncestralDiscreteScheduler:
         r1 = math.sqrt(1.0 + s1 * s1)
         return alpha_s, sigma_s, r * s_down / (s * r1), -(1.0 - s_down / s) / r1, s_up / r1
 
-    def noise_coefficients(self, j):
-        """(a_j, s_j) = (1, sigma_j) / sqrt(1 + sigma_j^2) of sigmas[j]: the variance-preserving pair of the frame the
-        loop runs in (x_vp = x_ve / sqrt(1 + sigma^2)); j = number of steps: the final sigma = 0, (1, 0)."""
-        n = self.num_inference_steps
-        if n is None:
-            raise RuntimeError("call set_timesteps() first")
-        if not 0 <= j <= n:
-            raise IndexError(f"step index {j} outside [0, {n}]")
-        sg = float(self.sigmas[j])
-        a = 1.0 / math.sqrt(sg * sg + 1.0)
-        return a, sg * a
-
-    def add_noise(self, original_samples, noise, timesteps):
-        """diffusers' EulerAncestralDiscreteScheduler.add_noise, in the scheduler's own (VE) frame: x0 + sigma noise at
-        the schedule's own timesteps (one, or one per sample of the batch)."""
-        own = [float(t) for t in self.timesteps.tolist()]
-        sig = []
-        for t in _timestep_list(timesteps):
-            if t not in own:
-                raise ValueError(f"timestep {t} is not in this schedule")
-            sig.append(float(self.sigmas[own.index(t)]))
-        return original_samples + _per_sample(sig, original_samples) * noise
-
-    def frame_scale(self, i):
-        """sqrt(1 + sigmas[i]^2): x_ve = frame_scale(i) x_vp at step index i (1 at the final sigma = 0)."""
-        s = float(self.sigmas[i])
-        return math.sqrt(1.0 + s * s)
+    def loop_steps(self, timesteps, begin_index, eta=0.0, init=False):
+        self._no_eta(eta)
+        return "ancestral", [self.ancestral_coefficients(begin_index + i) for i in range(len(timesteps))]
 
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, **unused):
         """One update on tensors in the VE frame (v-prediction `model_output`, diffusers' arithmetic in float32), noise
@@ -513,122 +553,6 @@ def lms_integrals(sg, i, order):
     return out
 
 
-class _SigmaScheduler:
-    """What the two deterministic samplers of the sigma (VE) parametrisation share with EulerAncestralDiscreteScheduler:
-    the clamped zero-SNR table, sigmas = table[timesteps] + [0], init_noise_sigma = the largest sigma, the UNet input
-    x / sqrt(1 + sigma^2), and the VP pair and frame scale the loop asks for."""
-    order = 1
-
-    def _tables(self, num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr):
-        self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
-        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, 0)
-        if rescale_betas_zero_snr:
-            # the zero-SNR table ends at alphas_cumprod = 0: clamped so that the first sigma is finite (4096)
-            self.alphas_cumprod[-1] = 2 ** -24
-        # sigma(t) = sqrt((1 - abar_t) / abar_t) in float32, as diffusers computes it
-        self.sigma_table = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
-        self.sigmas = torch.cat([self.sigma_table.flip(0), torch.zeros(1)]).to(torch.float32)
-        self.timesteps = torch.linspace(0, num_train_timesteps - 1, num_train_timesteps,
-                                        dtype=torch.float64).flip(0).to(torch.float32)
-        self.num_inference_steps = None
-        self._reset()
-
-    @classmethod
-    def from_config(cls, cfg, **overrides):
-        """From a dict or another scheduler's `config` (e.g. `DDIMScheduler(...).config`)."""
-        cfg = dict(cfg) if isinstance(cfg, dict) else dict(vars(cfg))
-        cfg.update(overrides)
-        return cls(**cfg)
-
-    def _reset(self):
-        self._step_index = None
-        self._begin_index = None
-        self._taken = 0
-        self._derivatives = []
-
-    @property
-    def init_noise_sigma(self):
-        """diffusers: the largest sigma under "linspace" / "trailing" spacing (a float32 tensor)."""
-        return self.sigmas.max()
-
-    @property
-    def step_index(self):
-        return self._step_index
-
-    @property
-    def begin_index(self):
-        return self._begin_index
-
-    def set_begin_index(self, begin_index=0):
-        self._begin_index = begin_index
-
-    def set_timesteps(self, num_inference_steps, device=None):
-        T = self.config.num_train_timesteps
-        self.num_inference_steps = num_inference_steps
-        ts = np.arange(T, 0, -T / num_inference_steps).round().astype(np.float32) - 1
-        self.timesteps = torch.from_numpy(ts.copy())
-        sig = self.sigma_table[self.timesteps.long()]
-        self.sigmas = torch.cat([sig, torch.zeros(1)]).to(torch.float32)
-        self._reset()
-
-    def _init_step_index(self, timestep):
-        if self._begin_index is not None:
-            self._step_index = self._begin_index
-            return
-        hits = (self.timesteps == float(timestep)).nonzero()
-        if len(hits) == 0:
-            raise ValueError(f"timestep {float(timestep)} is not in this schedule")
-        self._step_index = int(hits[1 if len(hits) > 1 else 0])
-
-    def scale_model_input(self, sample, timestep=None):
-        """x_ve -> x_vp = x_ve / sqrt(1 + sigma^2) at the current step (diffusers' scaling of the UNet input)."""
-        if self._step_index is None:
-            self._init_step_index(timestep)
-        sigma = self.sigmas[self._step_index]
-        return sample / ((sigma ** 2 + 1) ** 0.5)
-
-    def _check_index(self, i, begin_index=0, closed=False):
-        n = self.num_inference_steps
-        if n is None:
-            raise RuntimeError("call set_timesteps() first")
-        if not begin_index <= i < n + (1 if closed else 0):
-            raise IndexError(f"step index {i} outside [{begin_index}, {n}{']' if closed else ')'}")
-
-    def _vp(self, j):
-        """(a, s) = (1, sigma) / sqrt(1 + sigma^2) of sigmas[j], in float64."""
-        sg = float(self.sigmas[j])
-        a = 1.0 / math.sqrt(sg * sg + 1.0)
-        return a, sg * a
-
-    def noise_coefficients(self, j):
-        """(a_j, s_j) = (1, sigma_j) / sqrt(1 + sigma_j^2) of sigmas[j]: the variance-preserving pair of the frame the
-        loop runs in (x_vp = x_ve / sqrt(1 + sigma^2)); j = number of steps: the final sigma = 0, (1, 0)."""
-        self._check_index(j, closed=True)
-        return self._vp(j)
-
-    def add_noise(self, original_samples, noise, timesteps):
-        """diffusers' add_noise in the scheduler's own (VE) frame: x0 + sigma noise at the schedule's own timesteps (one,
-        or one per sample of the batch)."""
-        own = [float(t) for t in self.timesteps.tolist()]
-        sig = []
-        for t in _timestep_list(timesteps):
-            if t not in own:
-                raise ValueError(f"timestep {t} is not in this schedule")
-            sig.append(float(self.sigmas[own.index(t)]))
-        return original_samples + _per_sample(sig, original_samples) * noise
-
-    def frame_scale(self, i):
-        """sqrt(1 + sigmas[i]^2): x_ve = frame_scale(i) x_vp at step index i (1 at the final sigma = 0)."""
-        s = float(self.sigmas[i])
-        return math.sqrt(1.0 + s * s)
-
-    def _derivative(self, model_output, sample, i):
-        """diffusers' v-prediction arithmetic in the VE frame: (x0, d = (x - x0) / sigma = eps), float64 scalars."""
-        sigma = float(self.sigmas[i])
-        x0 = model_output * (-sigma / math.sqrt(sigma * sigma + 1.0)) + sample / (sigma * sigma + 1.0)
-        return x0, (sample - x0) / sigma
-
-
 class EulerDiscreteScheduler(_SigmaScheduler):
     """Euler sampling for the zero-terminal-SNR v-prediction schedule: the arithmetic of diffusers==0.29.2
     `EulerDiscreteScheduler` restated for the options listed in `__init__` (any other value raises NotImplementedError
@@ -647,39 +571,36 @@ class EulerDiscreteScheduler(_SigmaScheduler):
                  rescale_betas_zero_snr=False, final_sigmas_type="zero", **unused):
         # (clip_sample, set_alpha_to_one, ... of a DDIM configuration are not parameters of this sampler: ignored, as
         # diffusers' from_config does)
-        for name, value, ok in (("trained_betas", trained_betas, trained_betas is None),
-                                ("beta_schedule", beta_schedule, beta_schedule in ("linear", "scaled_linear")),
-                                ("prediction_type", prediction_type, prediction_type == "v_prediction"),
-                                ("interpolation_type", interpolation_type, interpolation_type == "linear"),
-                                ("use_karras_sigmas", use_karras_sigmas, not use_karras_sigmas),
-                                ("sigma_min", sigma_min, sigma_min is None),
-                                ("sigma_max", sigma_max, sigma_max is None),
-                                ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing"),
-                                ("timestep_type", timestep_type, timestep_type == "discrete"),
-                                ("final_sigmas_type", final_sigmas_type, final_sigmas_type == "zero")):
-            if not ok:
-                raise NotImplementedError(f"EulerDiscreteScheduler: {name}={value!r} is not built")
+        self._check_options(("trained_betas", trained_betas, trained_betas is None),
+                            ("beta_schedule", beta_schedule, beta_schedule in ("linear", "scaled_linear")),
+                            ("prediction_type", prediction_type, prediction_type == "v_prediction"),
+                            ("interpolation_type", interpolation_type, interpolation_type == "linear"),
+                            ("use_karras_sigmas", use_karras_sigmas, not use_karras_sigmas),
+                            ("sigma_min", sigma_min, sigma_min is None),
+                            ("sigma_max", sigma_max, sigma_max is None),
+                            ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing"),
+                            ("timestep_type", timestep_type, timestep_type == "discrete"),
+                            ("final_sigmas_type", final_sigmas_type, final_sigmas_type == "zero"))
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                                       beta_schedule=beta_schedule, prediction_type=prediction_type,
                                       interpolation_type=interpolation_type, use_karras_sigmas=use_karras_sigmas,
                                       timestep_spacing=timestep_spacing, timestep_type=timestep_type,
                                       steps_offset=steps_offset, rescale_betas_zero_snr=rescale_betas_zero_snr,
                                       final_sigmas_type=final_sigmas_type)
-        self._tables(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
+        self._sigma_tables()
 
     def linear_coefficients(self, i, begin_index=0):
         """LinearStep of step index i: k_x = a' a + s' s, k_v = s' a - a' s, no history.  Float64 arithmetic on the
         float32 sigmas; a step that ends at sigma = 0 is x0 itself, (k_x, k_v) = (a, -s)."""
         self._check_index(i, begin_index)
-        (a, s), (a1, s1) = self._vp(i), self._vp(i + 1)
+        (a, s), (a1, s1) = self._vp_at(i), self._vp_at(i + 1)
         return _linear_step(a1 * a + s1 * s, s1 * a - a1 * s)
 
     def step(self, model_output, timestep, sample, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0,
              generator=None, return_dict=True, **unused):
         """One update on tensors in the VE frame (v-prediction `model_output`): x + d (sigma' - sigma), keeping the step
         index like diffusers."""
-        if s_churn != 0.0:
-            raise NotImplementedError(f"EulerDiscreteScheduler.step: s_churn={s_churn!r} is not built")
+        self._check_options(("s_churn", s_churn, s_churn == 0.0))
         if self._step_index is None:
             self._init_step_index(timestep)
         i = self._step_index
@@ -708,20 +629,18 @@ class LMSDiscreteScheduler(_SigmaScheduler):
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                  trained_betas=None, use_karras_sigmas=False, prediction_type="epsilon", timestep_spacing="linspace",
                  steps_offset=0, rescale_betas_zero_snr=False, lms_order=4, **unused):
-        for name, value, ok in (("trained_betas", trained_betas, trained_betas is None),
-                                ("beta_schedule", beta_schedule, beta_schedule in ("linear", "scaled_linear")),
-                                ("use_karras_sigmas", use_karras_sigmas, not use_karras_sigmas),
-                                ("prediction_type", prediction_type, prediction_type == "v_prediction"),
-                                ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing"),
-                                ("lms_order", lms_order, lms_order in (1, 2, 3, 4))):
-            if not ok:
-                raise NotImplementedError(f"LMSDiscreteScheduler: {name}={value!r} is not built")
+        self._check_options(("trained_betas", trained_betas, trained_betas is None),
+                            ("beta_schedule", beta_schedule, beta_schedule in ("linear", "scaled_linear")),
+                            ("use_karras_sigmas", use_karras_sigmas, not use_karras_sigmas),
+                            ("prediction_type", prediction_type, prediction_type == "v_prediction"),
+                            ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing"),
+                            ("lms_order", lms_order, lms_order in (1, 2, 3, 4)))
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                                       beta_schedule=beta_schedule, use_karras_sigmas=use_karras_sigmas,
                                       prediction_type=prediction_type, timestep_spacing=timestep_spacing,
                                       steps_offset=steps_offset, rescale_betas_zero_snr=rescale_betas_zero_snr,
                                       lms_order=lms_order)
-        self._tables(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
+        self._sigma_tables()
 
     def order_at(self, i, begin_index=0):
         """min(i - begin_index + 1, lms_order): the number of derivatives the update of step index i combines in a run
@@ -738,7 +657,7 @@ class LMSDiscreteScheduler(_SigmaScheduler):
         (i - begin_index - j) % 3 and eps_i written to slot (i - begin_index) % 3 - at fourth order the slot of
         eps_{i-3}, read by the same update.  lms_order 1 keeps no history."""
         L = self.lms_coefficients(i, begin_index)
-        (a, s), (a1, _) = self._vp(i), self._vp(i + 1)
+        (a, s), (a1, _) = self._vp_at(i), self._vp_at(i + 1)
         E = float(self.sigmas[i + 1]) - sum(L[1:])                 # sigma_i + L_0
         r = i - begin_index
         reads = [((r - j) % 3, a1 * L[j]) for j in range(1, len(L))]
@@ -765,7 +684,7 @@ class LMSDiscreteScheduler(_SigmaScheduler):
 _PLMS = {1: (1.0,), 2: (3 / 2, -1 / 2), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}
 
 
-class PNDMScheduler:
+class PNDMScheduler(_AlphaScheduler):
     """PNDM's linear multistep part (PLMS) for the zero-terminal-SNR v-prediction schedule: the arithmetic of
     diffusers==0.29.2 `PNDMScheduler` with `skip_prk_steps=True`, restated for the options listed in `__init__` (any other
     value raises NotImplementedError naming the option - diffusers' default skip_prk_steps=False, the Runge-Kutta warm-up,
@@ -776,38 +695,24 @@ class PNDMScheduler:
     entry 1 redoes it from the saved sample with the mean of the two outputs, entries 2, 3, >= 4 are Adams-Bashforth of
     order 2, 3, 4 over the stored outputs.  The loop runs it with `vx_overlap_linear_step`, fed by
     `linear_coefficients(n)`; `step()` is the stateful diffusers-style tensor API."""
-    order = 1
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                  trained_betas=None, skip_prk_steps=False, set_alpha_to_one=False, prediction_type="epsilon",
                  timestep_spacing="leading", steps_offset=0, rescale_betas_zero_snr=False, **unused):
-        for name, value, ok in (("trained_betas", trained_betas, trained_betas is None),
-                                ("beta_schedule", beta_schedule, beta_schedule in ("linear", "scaled_linear")),
-                                ("skip_prk_steps", skip_prk_steps, bool(skip_prk_steps)),
-                                ("prediction_type", prediction_type, prediction_type == "v_prediction"),
-                                ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing")):
-            if not ok:
-                raise NotImplementedError(f"PNDMScheduler: {name}={value!r} is not built")
-        self.betas = _betas(num_train_timesteps, beta_start, beta_end, beta_schedule, rescale_betas_zero_snr)
-        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, 0)
-        self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
+        self._check_options(("trained_betas", trained_betas, trained_betas is None),
+                            ("beta_schedule", beta_schedule, beta_schedule in ("linear", "scaled_linear")),
+                            ("skip_prk_steps", skip_prk_steps, bool(skip_prk_steps)),
+                            ("prediction_type", prediction_type, prediction_type == "v_prediction"),
+                            ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing"))
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                                       beta_schedule=beta_schedule, skip_prk_steps=skip_prk_steps,
                                       set_alpha_to_one=set_alpha_to_one, prediction_type=prediction_type,
                                       timestep_spacing=timestep_spacing, steps_offset=steps_offset,
                                       rescale_betas_zero_snr=rescale_betas_zero_snr)
-        self.init_noise_sigma = 1.0
+        self._tables(sigma=False)
         self.pndm_order = 4
-        self.num_inference_steps = None
         self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1)
         self._reset()
-
-    @classmethod
-    def from_config(cls, cfg, **overrides):
-        """From a dict or another scheduler's `config` (e.g. `DDIMScheduler(...).config`)."""
-        cfg = dict(cfg) if isinstance(cfg, dict) else dict(vars(cfg))
-        cfg.update(overrides)
-        return cls(**cfg)
 
     def _reset(self):
         self.counter = 0
@@ -819,13 +724,10 @@ class PNDMScheduler:
         reverse(t[:-1] + t[-2:-1] + t[-1:]) - N + 1 entries for N >= 2, the second one repeated."""
         T = self.config.num_train_timesteps
         self.num_inference_steps = num_inference_steps
-        t = (np.round(np.arange(T, 0, -T / num_inference_steps))[::-1].astype(np.int64) - 1)
+        t = _trailing(T, num_inference_steps, np.int64)[::-1]
         ts = np.concatenate([t[:-1], t[-2:-1], t[-1:]])[::-1].copy()
         self.timesteps = torch.from_numpy(ts)
         self._reset()
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
 
     def _abar(self, t):
         return float(self.alphas_cumprod[t]) if t >= 0 else float(self.final_alpha_cumprod)
@@ -840,10 +742,7 @@ class PNDMScheduler:
         return al1 * al + s1 * s, s1 * al - al1 * s
 
     def _entry(self, n):
-        if self.num_inference_steps is None:
-            raise RuntimeError("call set_timesteps() first")
-        if not 0 <= n < len(self.timesteps):
-            raise IndexError(f"entry {n} outside [0, {len(self.timesteps)})")
+        self._check_index(n, n=len(self.timesteps))
         t, r = int(self.timesteps[n]), self.config.num_train_timesteps // self.num_inference_steps
         return (t + r, t) if n == 1 else (t, t - r)
 
@@ -851,9 +750,7 @@ class PNDMScheduler:
         """LinearStep of entry n (diffusers' `counter`) of the timestep list.  The history holds the averaged model
         output itself, (p_x, p_v) = (0, 1); the k-th output stored (entry 0, then entries 2, 3, ...) goes to ring slot
         k % 3 - at fourth order the slot of the oldest one, read by the same update."""
-        if begin_index != 0:
-            raise NotImplementedError("PNDMScheduler: begin_index != 0 (strength < 1): the warm-up pair of entries is not "
-                                      "defined for a run that starts inside the schedule")
+        self._check_start(begin_index)
         k_x, g = self._transfer(*self._entry(n))
         if n == 0:
             return _linear_step(k_x, g, h_write=0, saved_mode=1, p=(0.0, 1.0))
@@ -864,22 +761,20 @@ class PNDMScheduler:
         reads = [((k - j) % 3, g * w[j]) for j in range(1, len(w))]
         return _linear_step(k_x, g * w[0], reads, h_write=k % 3, p=(0.0, 1.0))
 
-    def noise_coefficients(self, j):
-        """(a_j, s_j) = (sqrt(abar), sqrt(1 - abar)) of timesteps[j], the level the latents have at entry j;
-        j = len(timesteps): the level after the last entry (final_alpha_cumprod)."""
-        n = len(self.timesteps)
-        if not 0 <= j <= n:
-            raise IndexError(f"entry {j} outside [0, {n}]")
-        abar = self._abar(int(self.timesteps[j]) if j < n else -1)
-        return math.sqrt(abar), math.sqrt(1.0 - abar)
+    def _check_start(self, begin_index, init=False):
+        """The first two entries are a pair (an Euler step, redone from the saved sample): a run that starts inside the
+        schedule has none.  NotImplementedError for begin_index != 0 (strength < 1) or an init clip."""
+        if begin_index != 0:
+            raise NotImplementedError("PNDMScheduler: begin_index != 0 (strength < 1) is not built: the warm-up pair of "
+                                      "entries is not defined for a run that starts inside the schedule")
+        if init:
+            raise NotImplementedError("PNDMScheduler: init-video sampling (known / init_video / init_latents) is not built: "
+                                      "the warm-up pair of entries is not defined for a run that starts from a noised clip")
 
-    def add_noise(self, original_samples, noise, timesteps):
-        """diffusers' PNDMScheduler.add_noise: sqrt(abar_t) x0 + sqrt(1 - abar_t) noise, t one timestep or one per sample
-        of the batch."""
-        abar = [float(self.alphas_cumprod[int(t)]) for t in _timestep_list(timesteps)]
-        a = _per_sample([math.sqrt(v) for v in abar], original_samples)
-        s = _per_sample([math.sqrt(1.0 - v) for v in abar], original_samples)
-        return a * original_samples + s * noise
+    def loop_steps(self, timesteps, begin_index, eta=0.0, init=False):
+        self._no_eta(eta)
+        self._check_start(begin_index, init)
+        return "linear", [self.linear_coefficients(i) for i in range(len(timesteps))]
 
     def step(self, model_output, timestep, sample, return_dict=True, **unused):
         """diffusers' step_plms on tensors (v-prediction `model_output`), keeping `counter`, `ets` and `cur_sample`."""
