@@ -1,8 +1,9 @@
 """fp8 projection GEMM problems whose correct answer is known exactly: e4m3 bytes, scales, a float64 reference, mutants, emulations.
 
 Host only (torch on any device, no import of v_express_amd): tests/test_fp8_gemm_cases_cpu.py shows that the cases are right and
-that they tell a subtly wrong fp8 GEMM from a right one.  They are made for vx_gemm (a_fp8 = 1) on every route (`ROUTES`,
-`kernel_operands`); the GPU file that feeds them to it is not part of the suite yet.  The counter hash, Geo / linear, round_el, Launch and the signs / rounding / saturated builders are gemm_cases' own.
+that they tell a subtly wrong fp8 GEMM from a right one; tests/test_gpu_fp8_gemm_exact.py feeds them to vx_gemm (a_fp8 = 1) on
+every route (`ROUTES`, `kernel_operands`) through tests/fp8_gemm_harness.py, which lays the operands out, judges and checks the
+fills on any device - the CPU file drives it with a stand-in for the kernel at the GPU file's shapes.  The counter hash, Geo / linear, round_el, Launch and the signs / rounding / saturated builders are gemm_cases' own.
 
 The main trick: a gemm_cases problem (A in {-1, 0, +1}, W in {-1, +1}, integer bias / rowbias, odd residual, alpha in {1, 0.5, 2})
 is handed to the kernel as e4m3 bytes with power-of-two scales hashed from the LOGICAL coordinates:
@@ -30,7 +31,7 @@ Cases that only fp8 has:
              The share with two candidates is a condition: the builder asserts it below 0.5 %.  (With a rowbias on top the sums
              cancel often enough for 0.61 % in float16 at K = 128: the rowbias launch runs `scales` without it.)  The one case
              that sees a scale product formed in the element type.
-  chained    (for the GPU: `chained` supplies x, w and the expected output) ops.quantize_fp8(x) and ops.fp8_weight(w) feed the GEMM at logical K in {40, 320, 640}: x and w hold
+  chained    (`chained` supplies x, w and the expected output; fp8_gemm_harness.judge_chained compares) ops.quantize_fp8(x) and ops.fp8_weight(w) feed the GEMM at logical K in {40, 320, 640}: x and w hold
              integers in [-7, 7] with a +-7 in every row, so amax / 448 = 2^-6 exactly, every quotient is an e4m3 value and the
              output is the exact integer product rounded once.  Pins that the producers' padding and scale conventions are the GEMM's.
 
@@ -161,6 +162,17 @@ class Fp8Case:
     def dequantised(self, dev="cpu", mut=None, emu=None):
         """float64 [m, n] and the scale product used: decode(q) decode(w8)^T a_scale w_scale, with a mutant of the decode, the K
         loop or the scale indices; emu: float32 arithmetic in one of the EMULATIONS' orders."""
+        if mut is None and emu is None:
+            # the plain reference is a function of the bytes and the scales - of (kind, m, n, K, density) - and read-only to
+            # its callers: one float64 product for all the cases of a launch that share them (gemm_cases' cache: G.clear_cache)
+            g = self.geo
+            key = ("fp8 dequantised", self.kind, g.m, g.n, g.k, self.base.dens, str(dev))
+            if key not in G._ACC:
+                G._ACC[key] = self._dequantise(dev, None, None)
+            return G._ACC[key]
+        return self._dequantise(dev, mut, emu)
+
+    def _dequantise(self, dev, mut, emu):
         g = self.geo
         q, w8 = self.bytes_(dev)
         ta = decode_table(dev, mut if mut in ("subnormals flushed on A", "0x80 decoded as NaN", "decode with exponent bias 8") else None)
@@ -301,10 +313,11 @@ def scales(g, el, dev="cpu"):
 
 
 PRODUCTS_GEO = linear(254, 256, 128)
+PRODUCTS_RING_GEO = linear(256, 320, 128)      # the persistent kernel takes whole 256 x 320 tiles only: rows and columns repeat
 
 
-def products(el, dev="cpu"):
-    c = Fp8Case("products", G.Case("products", PRODUCTS_GEO, el, 1.0))
+def products(el, dev="cpu", geo=PRODUCTS_GEO):
+    c = Fp8Case("products", G.Case("products", geo, el, 1.0))
     share = float(c.left_out(dev).double().mean())
     assert share <= PRODUCTS_CAP, f"products: {share:.4f} of the pairs left out"
     c.conditions.append(f"pairs left out (nonzero, below 2^-14): {share:.4f} (<= {PRODUCTS_CAP}); max |exact| "
@@ -462,10 +475,11 @@ def _split(s, t, c):
 def _routes():
     r = {}
     st = _key(K128, "STORE")
-    # (vx_gemm's general `n % 8 == 0` check refuses n = 4 today although its fp8 branch asks n % 4: to be settled with the GPU file)
-    # n = 4 and n = 136: the `n - 4` clamp of the scale / bias / residual loads; 328 = two tiles + 8 columns; 128 x 320 x 256:
-    # two K tiles with nothing padded, neither in rows nor in columns
-    r["128x160 store"] = [Launch(linear(m, n, k), st) for m, n, k in ((1, 4, 128), (127, 160, 128), (129, 136, 128), (257, 320, 384),
+    # n = 8 and n = 136: the `n - 4` clamp of the scale / bias / residual loads (at n = 8 the lanes with lq >= 2 clamp to column
+    # 4; vx_gemm refuses n % 8 != 0 for every operand type, and no fp8 producer of the model has such an n: n = 4 is a refusal
+    # test of the GPU file); 328 = two tiles + 8 columns; 128 x 320 x 256: two K tiles with nothing padded, neither in rows nor
+    # in columns
+    r["128x160 store"] = [Launch(linear(m, n, k), st) for m, n, k in ((1, 8, 128), (127, 160, 128), (129, 136, 128), (257, 320, 384),
                                                                        (130, 1280, 1280), (300, 328, 640), (128, 320, 256))]
     # 256 tiles, the last with one row; 86 x 3 = 258 tiles
     r["256x320 store"] = [Launch(linear(65281, 320, 128), _key(K256, "STORE")), Launch(linear(256 * 86, 960, 384), _key(K256, "STORE"))]

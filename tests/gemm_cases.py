@@ -305,6 +305,13 @@ class Case:
     folded: bool = False
     conditions: list = field(default_factory=list)        # what the builder verified, for the CPU file's printout
 
+    def __post_init__(self):
+        # the rowbias table has m // rows_per_group rows and `exact` reads row m' // rows_per_group of it: the groups must be
+        # whole, or the last rows would read one past its end (an IndexError on the CPU, an aborted indexing kernel on a GPU)
+        g = self.geo
+        assert g.rows_per_group >= 0 and (not g.rows_per_group or g.m % g.rows_per_group == 0), \
+            f"{self.name} {g.text()}: m={g.m} is no multiple of rows_per_group={g.rows_per_group}: the last rowbias group is not whole"
+
     # ---- operands (float64, on dev)
     def bias(self, dev):
         g, j = self.geo, _ar(self.geo.n, dev)

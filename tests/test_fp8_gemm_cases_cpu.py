@@ -1,7 +1,7 @@
 """tests/fp8_gemm_cases.py on the CPU: the exact-answer fp8 GEMM cases are right, and they catch what the aggregate bounds miss.
 
-For every geometry of fp8_gemm_cases.ROUTES (the launches a GPU file is to make; here with `reduced` row counts, n and K
-unchanged), `products`, and both element types:
+For every geometry of fp8_gemm_cases.ROUTES (the launches tests/test_gpu_fp8_gemm_exact.py makes; here with `reduced` row
+counts, n and K unchanged), `products`, and both element types:
   (a) consistency: the encoded bytes decode back to gemm_cases' integers times the scales, the expected outputs computed from the
       BYTES are gemm_cases' own, every expected value is the float64 value rounded once, and the decode table from the format's
       formula is torch.float8_e4m3fn's;
@@ -12,7 +12,12 @@ unchanged), `products`, and both element types:
   (d) every mutant of the reference (fp8_gemm_cases.MUTANTS) violates at least one case on at least one route shape - which case
       and which shape is printed; the dropped half K tile is missed at logical K = 320 and caught at K = 128, 256 and 640; the
       scale product rounded to the element type is caught by `scales` only;
-  (e) for the record, on Gaussian data: which mutants the bound of test_gpu_kernels.py::test_gemm_fp8_store_and_split accepts.
+  (e) for the record, on Gaussian data: which mutants the bound of test_gpu_kernels.py::test_gemm_fp8_store_and_split accepts;
+  (f) the GPU file's own path on the host: tests/fp8_gemm_harness.py - the operands' layout, the expected outputs, the judging and
+      the fill checks of tests/test_gpu_fp8_gemm_exact.py, everything but the library call - with a float32 stand-in for the
+      kernel, every launch of up to 1024 rows at its FULL shape (the rest `reduced`): an index that leaves its table is an
+      IndexError here before it can reach a GPU (a rowbias group that is not whole is refused where the case is built), and
+      stand-ins built from MUTANTS fail through the same harness, one per judged kind.
 
 Measured here (bfloat16, test_gemm_fp8_store_and_split's operand recipe - Gaussian a, Gaussian w K^-1/2, scale = row amax / 448,
 bias, residual, alpha = 0.95, plus a two-group rowbias for the rowbias mutant - at 128 x 320; max|err| / allowed and relL2 /
@@ -48,6 +53,7 @@ import pytest
 import torch
 
 import fp8_gemm_cases as P
+import fp8_gemm_harness as H
 import gemm_cases as G
 
 ROUTE_NAMES = sorted(P.ROUTES)
@@ -258,6 +264,92 @@ def test_old_bound_figures(capsys):
                  "w_scale[n - 4 .. n - 1] for the four columns before them"):
         assert not any(passes[name]), f"'{name}' passes the old bound somewhere: this record is out of date"
     assert passes["upper 64 bytes of the last K tile dropped"] == [True, False, False]
+
+
+# ----------------------------------------------------------------------------------------------------- the GPU file's path, on the host
+def host_shape(g):
+    """Full shape up to 1024 rows - the launches whose m `reduced` changes, the odd tails among them - and `reduced` beyond."""
+    return g if g.m <= 1024 else P.reduced(g)
+
+
+def test_partial_rowbias_group_is_refused_where_the_case_is_built():
+    """m = 130 in groups of 16: row 128 would read row 8 of a rowbias table of 8 rows."""
+    g = G.linear(130, 160, 128, rows_per_group=16)
+    with pytest.raises(AssertionError, match=r"m=130 is no multiple of rows_per_group=16"):
+        G.signs(g, torch.bfloat16, "cpu", residual=True)
+    with pytest.raises(AssertionError, match=r"m=130 is no multiple of rows_per_group=16"):
+        P.Fp8Case("pow2", G.Case("signs", g, torch.bfloat16, 1.0))
+    for routes in (G.ROUTES, P.ROUTES):                    # no launch of either file's routes has one, at its full shape
+        for name, launches in routes.items():
+            for l in launches:
+                assert not l.geo.rows_per_group or l.geo.m % l.geo.rows_per_group == 0, (name, l.geo.text())
+
+
+@pytest.mark.parametrize("route", ROUTE_NAMES)
+def test_harness_with_a_host_stand_in(route):
+    """tests/fp8_gemm_harness.py - all that tests/test_gpu_fp8_gemm_exact.py does but the library call - with a stand-in for
+    the kernel: an index that leaves its table fails here.  Every launch of the route at `host_shape`, both element types; the
+    stand-in is the 'K tiles forwards' design of EMULATIONS (float32), and a second time float32 arithmetic on the tensors of
+    the call themselves, which shows that the laid-out operands are the problem the expected outputs belong to."""
+    for el in G.ELEMS:
+        for stand_in in (H.reference_stand_in("cpu", emu="K tiles forwards"), H.operand_stand_in):
+            failures, made = H.run_route(route, el, stand_in, "cpu", shape=host_shape)
+            assert made >= 2 * len(P.ROUTES[route])
+            assert not failures, f"{len(failures)} (route, shape, case) triples fail:\n" + "\n".join(failures)
+
+
+def test_harness_products_and_chained_with_a_host_stand_in():
+    for el in G.ELEMS:
+        for geo in (P.PRODUCTS_GEO, P.PRODUCTS_RING_GEO):
+            for stand_in in (H.reference_stand_in("cpu", emu="K tiles backwards"), H.operand_stand_in):
+                assert H.run_case(P.products(el, geo=geo), "products", stand_in, "cpu") is None
+        for m, n, k in P.CHAINED:
+            def produce(x, w):                             # amax / 448 scales and exact quotients, as the producers make them
+                sa, sw = x.double().abs().amax(dim=1) / 448.0, w.double().abs().amax(dim=1) / 448.0
+                qa, qw = x.double() / sa[:, None], w.double() / sw[:, None]
+                assert torch.equal(qa.float().to(torch.float8_e4m3fn).double(), qa)
+                return ((qa @ qw.t()) * sa[:, None] * sw[None, :]).float().to(el), sa.float(), sw.float()
+            assert H.judge_chained(m, n, k, el, "cpu", produce) is None
+
+
+def test_harness_fails_on_a_wrong_stand_in():
+    """That the GPU file checks anything: stand-ins built from MUTANTS fail through the same harness, one per judged kind,
+    with a message naming route, shape, case and the first wrong element."""
+    el = torch.bfloat16
+    # pow2 (==): every case of the route's launches that the mutant can touch fails
+    failures, made = H.run_route("128x160 store", el, H.reference_stand_in("cpu", mut="truncating store"), "cpu", shape=P.reduced)
+    assert len(failures) >= len(P.ROUTES["128x160 store"]) and made > len(failures)
+    msg = [f for f in failures if "rounding + residual" in f and "K=1280" in f][0]
+    for part in ("128x160 store (gemm_kernel<128x160x128,4w,STORE,fast,fp8>)", "rounding + residual [bf16]", "-> 1280 [m=40 K=1280 store]",
+                 "out:", "first at (", "got ", "expected "):
+        assert part in msg, (part, msg)
+    # scales (the band): the one case that sees a scale product formed in the element type
+    failures, _ = H.run_route("128x160 store", el, H.reference_stand_in("cpu", mut="scale product rounded to the element type"),
+                              "cpu", shape=P.reduced)
+    assert failures and all(": scales [bf16]" in f for f in failures), failures
+    # products (==, float16 with its left-out pairs): a flushed subnormal and a dropped half K tile
+    for e in G.ELEMS:
+        for mut in ("subnormals flushed on W", "upper 64 bytes of the last K tile dropped"):
+            msg = H.run_case(P.products(e), "products", H.reference_stand_in("cpu", mut=mut), "cpu")
+            assert msg is not None and msg.startswith(f"products [{G.EL_NAME[e]}]") and "first at (" in msg, (mut, msg)
+    # ... and a stand-in that writes beside its output, into the residual, or reads a wrong rowbias group
+    case = P.in_place(G.linear(48, 160, 128), el)
+
+    def beside(call):
+        H.operand_stand_in(call)
+        call.guards[-1][1][5, 3] = 0.0
+    assert "the fill beside residual was written" in H.run_case(case, "k", beside, "cpu", in_place=True)
+
+    def shifted_group(call):
+        call.rows_per_group += 1
+        H.operand_stand_in(call)
+    assert "in place: signs + residual [bf16]" in H.run_case(case, "k", shifted_group, "cpu", in_place=True)
+    store = P.cases(G.linear(48, 160, 128), el)[1]
+
+    def into_residual(call):
+        H.operand_stand_in(call)
+        call.residual[7, 7] += 2
+    assert "the operand residual was written" in H.run_case(store, "k", into_residual, "cpu")
 
 
 def test_failure_message_names_the_element():

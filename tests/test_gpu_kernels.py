@@ -705,7 +705,8 @@ def test_layernorm_fp8(ops, rows, c, norm, pe):
 def test_gemm_fp8_store_and_split(ops, m, n, k):
     """The fp8 GEMM against a float64 product of the DEQUANTISED operands (e4m3 x e4m3 products are exact in fp32, so
     only the accumulation order and the bf16 output rounding remain): per-kernel tolerance of the bf16 GEMM.
-    (What this bound lets through, and exact-answer cases for the fp8 GEMM: tests/test_fp8_gemm_cases_cpu.py, tests/fp8_gemm_cases.py.)"""
+    (What this bound lets through: tests/test_fp8_gemm_cases_cpu.py; the exact-answer cases on every fp8 route:
+    tests/test_gpu_fp8_gemm_exact.py, tests/fp8_gemm_cases.py.)"""
     a = rnd(m, k, seed=1)
     w = rnd(n, k, scale=k ** -0.5, seed=2)
     a8, w8 = ops.quantize_fp8(a), ops.fp8_weight(w)
@@ -740,7 +741,7 @@ def test_gemm_fp8_ring_vs_classic_tiles(ops):
     """The persistent ring kernel's fp8 instantiation (opt-in: it spills and measures slower than the classic fp8 tiles;
     requested per call here - ops.FP8_RING -> vx_gemm_params.ring_hint = 3, ABI 14 - so that every model-level fp8 test
     runs the product default) against the classic fp8 tiles and the float64 reference of the dequantised operands.
-    (Exact-answer cases and the ring route's shapes: tests/fp8_gemm_cases.py.)"""
+    (Exact-answer cases on the ring route's shapes: tests/test_gpu_fp8_gemm_exact.py, tests/fp8_gemm_cases.py.)"""
     from v_express_amd import lib as L
     m, n, k = 256 * 200, 640, 640
     a8, w8 = ops.quantize_fp8(rnd(m, k, seed=1)), ops.fp8_weight(rnd(n, k, scale=k ** -0.5, seed=2))

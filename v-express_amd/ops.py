@@ -728,6 +728,12 @@ def gemm(a, w, bias=None, *, geom=None, a2=None, residual=None, alpha=1.0, act=L
     if rowbias is not None:
         if rowbias.dtype != torch.float32 or rowbias.stride(-1) != 1:
             raise TypeError("rowbias must be float32 with contiguous columns")
+        # the kernel reads rowbias + (row // rows_per_group) * rowbias_ld unchecked: the table must cover the last row's group
+        if rows_per_group <= 0:
+            raise ValueError(f"rowbias needs rows_per_group > 0, got {rows_per_group}")
+        if rowbias.dim() != 2 or rowbias.shape[1] != n or rowbias.shape[0] < -(-p.m // rows_per_group):
+            raise ValueError(f"rowbias {tuple(rowbias.shape)}: m={p.m} rows in groups of {rows_per_group} need "
+                             f"[{-(-p.m // rows_per_group)}, {n}]")
         p.rowbias, p.rowbias_ld, p.rows_per_group = rowbias.data_ptr(), rowbias.stride(0), rows_per_group
     if residual is not None:
         _chk_bf16(residual, "residual")
