@@ -4,6 +4,7 @@ with a chosen sampler and step count (GPU box):
     python tools/sampler_bench.py --scheduler dpm --steps 15 [--order 2]
     python tools/sampler_bench.py --scheduler euler-a --steps 25
     python tools/sampler_bench.py --scheduler euler|lms|pndm --steps 25 [--lms-order 4]
+    python tools/sampler_bench.py --scheduler unipc --steps 10 [--solver-order 2] [--solver-type bh2]
     python tools/sampler_bench.py --scheduler ddim-eta --eta 1.0 --steps 25
     python tools/sampler_bench.py --scheduler ddim --steps 25 --guidance-rescale 0.7 --guidance-end 0.6
     python tools/sampler_bench.py --scheduler ddim --steps 25 --init-video --strength 0.6 --mask lower-half
@@ -12,7 +13,7 @@ with a chosen sampler and step count (GPU box):
 Prints one JSON line: ms per clip (host clock around whole clips, ending in a device synchronise), the denoise and decode
 milliseconds of the same clips (HIP events), and the average microseconds of the per-step update launch (HIP events
 around each `ops.overlap_ddim_step` / `ops.overlap_multistep_step` / `ops.overlap_ancestral_step` /
-`ops.overlap_linear_step` (Euler, LMS, PNDM - whose list has steps + 1 entries) of one further, instrumented clip; for the ancestral samplers also `ddim_update_us`, the DDIM update of the same clip timed the same way,
+`ops.overlap_linear_step` (Euler, LMS, PNDM - whose list has steps + 1 entries) / `ops.overlap_unipc_step` of one further, instrumented clip; for the ancestral samplers also `ddim_update_us`, the DDIM update of the same clip timed the same way,
 for comparison).  The guidance controls (--guidance-rescale, --guidance-start, --guidance-end) are passed to the loop; the
 line then also carries them, the number of guided steps, `rescale_us` (the `ops.guidance_rescale` launches of a step,
 timed the same way; it stands in for the one `vx_combine_units` launch of a step without the rescale, `combine_us`) and
@@ -46,12 +47,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scheduler", choices=("ddim", "dpm", "ddim-eta", "euler-a", "euler", "lms", "pndm"),
+    ap.add_argument("--scheduler", choices=("ddim", "dpm", "ddim-eta", "euler-a", "euler", "lms", "pndm", "unipc"),
                     default="ddim")
     ap.add_argument("--eta", type=float, default=1.0, help="DDIM eta of --scheduler ddim-eta")
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--order", type=int, choices=(1, 2), default=2, help="DPM-Solver++ solver_order")
     ap.add_argument("--lms-order", type=int, choices=(1, 2, 3, 4), default=4, help="LMSDiscreteScheduler lms_order")
+    ap.add_argument("--solver-order", type=int, choices=(1, 2, 3), default=2, help="UniPCMultistepScheduler solver_order")
+    ap.add_argument("--solver-type", choices=("bh1", "bh2"), default="bh2", help="UniPCMultistepScheduler solver_type")
     ap.add_argument("--guidance-rescale", type=float, default=0.0, help="phi of the CFG rescale")
     ap.add_argument("--guidance-start", type=float, default=0.0)
     ap.add_argument("--guidance-end", type=float, default=1.0)
@@ -116,6 +119,9 @@ def main():
         sched, update = vx.LMSDiscreteScheduler(**kw, lms_order=args.lms_order), "overlap_linear_step"
     elif args.scheduler == "pndm":
         sched, update = vx.PNDMScheduler(**kw, skip_prk_steps=True), "overlap_linear_step"
+    elif args.scheduler == "unipc":
+        sched = vx.UniPCMultistepScheduler(**kw, solver_order=args.solver_order, solver_type=args.solver_type)
+        update = "overlap_unipc_step"
     else:
         sched, update = vx.DPMSolverMultistepScheduler(**kw, solver_order=args.order), "overlap_multistep_step"
     pipe = vx.VExpressPipeline(vae=vae, reference_net=refnet, denoising_unet=unet, scheduler=sched)
@@ -267,7 +273,7 @@ def main():
             pipe.scheduler, eta = sched_a, eta_a
     print(json.dumps(dict(
         scheduler=args.scheduler,
-        order=args.order if args.scheduler == "dpm" else args.lms_order if args.scheduler == "lms" else None,
+        order={"dpm": args.order, "lms": args.lms_order, "unipc": args.solver_order}.get(args.scheduler),
         eta=eta if args.scheduler == "ddim-eta" else None, steps=args.steps,
         config=f"512x512, {F} frames ({'one window' if len(windows) == 1 else f'{len(windows)} windows'}), "
                f"CFG {args.guidance_scale:g}, synthetic weights, bf16",

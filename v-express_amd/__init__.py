@@ -8,7 +8,7 @@ is missing.  Host-only helpers (synth, context, scheduler, distributed) import w
 """
 from .synth import UNetConfig, VaeConfig  # noqa: F401
 from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
-                        EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler)
+                        EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler, UniPCMultistepScheduler)
 
 _LAZY = {
     "UNet3DConditionModel": "unet_3d", "UNet3DConditionOutput": "unet_3d", "UNet2DConditionModel": "unet_2d",
@@ -28,4 +28,4 @@ def __getattr__(name):
 
 __all__ = ["UNetConfig", "VaeConfig", "DDIMScheduler", "DPMSolverMultistepScheduler",
            "EulerAncestralDiscreteScheduler", "EulerDiscreteScheduler", "LMSDiscreteScheduler",
-           "PNDMScheduler"] + list(_LAZY)
+           "PNDMScheduler", "UniPCMultistepScheduler"] + list(_LAZY)

@@ -1,5 +1,5 @@
 """Tensor-level wrappers around the C ABI (include/vexpress_hip.h, include/vexpress_hip_guidance.h,
-include/vexpress_hip_samplers.h).
+include/vexpress_hip_samplers.h, include/vexpress_hip_solvers.h).
 
 PyTorch is used for device memory and streams only: every wrapper passes raw device pointers, explicit
 shapes/strides and `torch.cuda.current_stream()` to libvexpress_hip.so.  Activations are bf16
@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import lib as L
-from .scheduler import LinearStep
+from .scheduler import LinearStep, UniPCStep
 
 class _CurrentLib:
     """`_lib.vx_*` resolves to the library of the element type in force (lib.ELEM: bfloat16 or IEEE half; lib.element_type)."""
@@ -1532,6 +1532,51 @@ def overlap_linear_step(latents, preds, terms, frame_ids, counts, history, saved
     L.check(_lib.vx_overlap_linear_step(_ptr(latents), c, F, h * w, _ptr(preds), preds.shape[2], _ptr(terms),
                                         terms.shape[1], _ptr(frame_ids), _ptr(counts), n, _ptr(history), *slots,
                                         _ptr(saved), coef.saved_mode, *scal, _stream()), "vx_overlap_linear_step")
+
+
+def overlap_unipc_step(latents, preds, terms, frame_ids, counts, history, saved, coef):
+    """UniPC update of `frame_ids` (vx_overlap_unipc_step, include/vexpress_hip_solvers.h): latents fp32 [1,C,F,h,w]
+    updated in place, preds fp32 [slots, C, f, hw]; history fp32 [3, C, F, h, w] (None when coef names no slot), saved fp32
+    shaped like latents (the corrected sample: read when coef.use_c, always written); coef a UniPCStep:
+        m = a_i x - s_i v;  xc = q_s saved + q_m m + q_1 H[h1] + q_2 H[h2] + q_3 H[h3] if use_c else x
+        out = k_x xc + k_m m + k_1 H[h1] + k_2 H[h2]
+    (a slot of -1 is skipped, its buffer not read), then saved <- xc and H[h_write] <- m."""
+    coef = UniPCStep(*coef)
+    for t, name in ((latents, "latents"), (preds, "preds"), (counts, "counts")):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError(f"overlap_unipc_step: contiguous float32 {name} expected")
+    for t, name in ((terms, "terms"), (frame_ids, "frame_ids")):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise TypeError(f"overlap_unipc_step: contiguous int32 {name} expected")
+    if latents.dim() != 5 or latents.shape[0] != 1 or preds.dim() != 4 or preds.shape[1] != latents.shape[1]:
+        raise ValueError("overlap_unipc_step: latents must be [1, C, F, h, w] and preds [slots, C, f, hw]")
+    _, c, F, h, w = latents.shape
+    n = frame_ids.numel()
+    if preds.shape[3] != h * w or (h * w) % 4:
+        raise ValueError(f"overlap_unipc_step: preds must hold h * w = {h * w} pixels per frame, a multiple of 4")
+    if terms.dim() != 3 or terms.shape[0] != n or terms.shape[1] < 1 or terms.shape[2] != 2 or counts.numel() != n or n < 1:
+        raise ValueError("overlap_unipc_step: terms must be [n, max_terms, 2] and counts [n] for the n frames of frame_ids")
+    slots = (coef.h1, coef.h2, coef.h3, coef.h_write)
+    for name, s in zip(("h1", "h2", "h3", "h_write"), slots):
+        if not (isinstance(s, int) and -1 <= s <= 2):
+            raise ValueError(f"overlap_unipc_step: {name} must be a history slot 0..2 or -1, got {s!r}")
+    if coef.use_c not in (0, 1):
+        raise ValueError(f"overlap_unipc_step: use_c must be 0 or 1, got {coef.use_c!r}")
+    if any(s >= 0 for s in slots) and history is None:
+        raise ValueError("overlap_unipc_step: the coefficients name a history slot, but history is None")
+    if saved is None:
+        raise ValueError("overlap_unipc_step: the saved buffer is written by every update, but saved is None")
+    if history is not None and (history.dtype != torch.float32 or not history.is_contiguous()
+                                or tuple(history.shape) != (3,) + tuple(latents.shape[1:])):
+        raise TypeError("overlap_unipc_step: history must be contiguous float32 [3, C, F, h, w]")
+    if saved.dtype != torch.float32 or not saved.is_contiguous() or saved.shape != latents.shape:
+        raise TypeError("overlap_unipc_step: saved must be contiguous float32 of the latents' shape")
+    scal = [float(v) for v in coef[5:]]
+    if not all(math.isfinite(v) for v in scal):
+        raise ValueError(f"overlap_unipc_step: the coefficients must be finite, got {tuple(coef)}")
+    L.check(_lib.vx_overlap_unipc_step(_ptr(latents), c, F, h * w, _ptr(preds), preds.shape[2], _ptr(terms),
+                                       terms.shape[1], _ptr(frame_ids), _ptr(counts), n, _ptr(history), *slots,
+                                       _ptr(saved), int(coef.use_c), *scal, _stream()), "vx_overlap_unipc_step")
 
 
 def overlap_blend(preds, terms, weights, out):

@@ -322,14 +322,15 @@ class VExpressPipeline:
 
     # ------------------------------------------------------------------ the hot loop
     def _sampler(self, eta=0.0):
-        """The fused update the loop runs with this scheduler and eta - "ddim", "multistep", "ancestral" or "linear", the
+        """The fused update the loop runs with this scheduler and eta - "ddim", "multistep", "ancestral", "linear" or "unipc", the
         scheduler's own answer (scheduler.loop_steps, here for a run of no steps; the caller asks again with its
         timesteps for the coefficients).  Any scheduler that is not one of the project's raises TypeError before anything
         runs: the fused updates are the only ones the loop has.  eta is honoured by DDIM only: the others raise
         NotImplementedError."""
         if not isinstance(self.scheduler, _Scheduler):
             raise TypeError(f"the denoising loop drives v_express_amd.DDIMScheduler or "
-                            f"v_express_amd.DPMSolverMultistepScheduler or v_express_amd.EulerAncestralDiscreteScheduler or "
+                            f"v_express_amd.DPMSolverMultistepScheduler or v_express_amd.UniPCMultistepScheduler or "
+                            f"v_express_amd.EulerAncestralDiscreteScheduler or "
                             f"v_express_amd.EulerDiscreteScheduler, LMSDiscreteScheduler or PNDMScheduler, "
                             f"not {type(self.scheduler).__name__}")
         return self.scheduler.loop_steps((), 0, eta)[0]
@@ -450,6 +451,9 @@ class VExpressPipeline:
         pair, one saved sample).  PNDM's timestep list has one entry more than num_inference_steps - the second timestep
         twice - and every entry is one timestep of the loop (the guidance interval counts them); it cannot start inside
         the schedule: begin_index != 0 or `known` raise NotImplementedError.
+        UniPC runs one vx_overlap_unipc_step per timestep: the corrector of the step that ended at the sample the UNet just
+        saw, then the predictor from the corrected sample; it keeps the data predictions of the last three steps per frame
+        and the corrected sample, and starts a run (begin_index) at first order without a corrector.
         Guidance controls (classifier-free guidance only; every sampler): step i of the N timesteps is guided iff
         i / N >= guidance_start and (i + 1) / N <= guidance_end, any other step computes the conditional rows only and
         takes them as the prediction; guidance_rescale = phi > 0 scales each window's guided prediction g by

@@ -158,8 +158,11 @@ class Sampler:
     `x0_hist`: identical on every rank, like the latents), "ancestral" (vx_overlap_ancestral_step, noise keyed by
     `noise_seed` and the step index) or "linear" (vx_overlap_linear_step, with `history`, three per-frame slots, and
     `saved`, PNDM's saved sample: allocated only when some step names them, never read before they are written, identical
-    on every rank).  A scheduler that has `frame_scale` (Euler ancestral, Euler, LMS): the latents come and go in its
-    (VE) frame and the loop runs in the VP frame x / sqrt(1 + sigma^2); None for the others."""
+    on every rank) or "unipc" (vx_overlap_unipc_step, with `history`, the data predictions of the last three steps of every
+    frame, and `saved`, the corrected sample the next corrector starts from: identical on every rank, never read before
+    they are written, and not touched by the known blend, like the DPM++ history).  A scheduler that has `frame_scale`
+    (Euler ancestral, Euler, LMS): the latents come and go in its (VE) frame and the loop runs in the VP frame
+    x / sqrt(1 + sigma^2); None for the others."""
 
     def __init__(self, scheduler, update, coefs, latents, begin_index, noise_seed):
         self.begin_index, self.steps, self.coefs = begin_index, len(coefs), coefs
@@ -173,8 +176,11 @@ class Sampler:
             self.history = torch.empty((3,) + tuple(latents.shape[1:]), device=latents.device,
                                        dtype=torch.float32) if slots else None
             self.saved = torch.empty_like(latents) if any(cf.saved_mode for cf in coefs) else None
+        elif update == "unipc":                       # (every update writes a history slot and the saved sample)
+            self.history = torch.empty((3,) + tuple(latents.shape[1:]), device=latents.device, dtype=torch.float32)
+            self.saved = torch.empty_like(latents)
         self._update = {"ddim": self._ddim, "multistep": self._multistep, "ancestral": self._ancestral,
-                        "linear": self._linear}[update]
+                        "linear": self._linear, "unipc": self._unipc}[update]
 
     def start(self, latents):
         if self.frame_scale is not None:
@@ -198,6 +204,10 @@ class Sampler:
     def _linear(self, i, latents, step_preds, stitch):
         ops.overlap_linear_step(latents, step_preds, stitch.terms, stitch.frame_ids, stitch.counts, self.history,
                                 self.saved, self.coefs[i])
+
+    def _unipc(self, i, latents, step_preds, stitch):
+        ops.overlap_unipc_step(latents, step_preds, stitch.terms, stitch.frame_ids, stitch.counts, self.history,
+                               self.saved, self.coefs[i])
 
     def callback_view(self, i, latents):
         """What a callback sees after step i: the scheduler's own (VE) frame for the sigma schedulers, as the reference's."""

@@ -10,14 +10,17 @@ second-order multistep sampler of the reference's scheduler list, pipelines/v_ex
 eta > 0 through `DDIMScheduler.ancestral_coefficients(t, eta)`, EulerAncestralDiscreteScheduler through
 `ancestral_coefficients(i)`) feed `vx_overlap_ancestral_step`, which draws its noise on the device.  The rest of the
 reference's list - EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler - are linear multistep updates in the loop's
-frame and feed `vx_overlap_linear_step` through `linear_coefficients(i, begin_index)`.
+frame and feed `vx_overlap_linear_step` through `linear_coefficients(i, begin_index)`.  UniPCMultistepScheduler - not on
+the reference's list: a predictor-corrector, one order higher than DPM-Solver++ at the same UNet evaluations - feeds
+`vx_overlap_unipc_step` through `unipc_coefficients(i, begin_index)`.
 
-What the classes share is stated once: `_Scheduler` (all six) holds `from_config`, the refusal of options that are not
+What the classes share is stated once: `_Scheduler` (all seven) holds `from_config`, the refusal of options that are not
 built, the beta / alphas_cumprod / sigma tables, the timestep -> step index lookup and the index checks, and the
-contract with the denoising loop, `loop_steps(timesteps, begin_index, eta, init)` -> (update, coefs): which of the four
-fused updates ("ddim", "multistep", "ancestral", "linear") the scheduler runs, the per-step coefficients that update
-takes, and every rule about eta or the start of a run that depends on the class.  `_AlphaScheduler` (DDIM, PNDM) adds the
-noise levels read from alphas_cumprod, `_SigmaScheduler` (Euler ancestral, Euler, LMS) the sigma (VE) parametrisation.
+contract with the denoising loop, `loop_steps(timesteps, begin_index, eta, init)` -> (update, coefs): which of the five
+fused updates ("ddim", "multistep", "ancestral", "linear", "unipc") the scheduler runs, the per-step coefficients that
+update takes, and every rule about eta or the start of a run that depends on the class.  `_AlphaScheduler` (DDIM, PNDM)
+adds the noise levels read from alphas_cumprod, `_LambdaScheduler` (DPM-Solver++, UniPC) the sigmas of the run in the
+variance-preserving frame, `_SigmaScheduler` (Euler ancestral, Euler, LMS) the sigma (VE) parametrisation.
 """
 from types import SimpleNamespace
 
@@ -71,7 +74,7 @@ def _vp(sigma):
 
 
 class _Scheduler:
-    """What all six schedulers share; a subclass sets `config` and then calls `_tables`."""
+    """What all seven schedulers share; a subclass sets `config` and then calls `_tables`."""
     order = 1
     init_noise_sigma = 1.0
 
@@ -125,7 +128,8 @@ class _Scheduler:
 
     def loop_steps(self, timesteps, begin_index, eta=0.0, init=False):
         """What the denoising loop runs for `timesteps`, the scheduler's own from step index `begin_index` on:
-        (update, coefs) - the fused update, one of "ddim", "multistep", "ancestral", "linear" (ops.overlap_<update>_step),
+        (update, coefs) - the fused update, one of "ddim", "multistep", "ancestral", "linear", "unipc"
+        (ops.overlap_<update>_step),
         and the list of per-step coefficients that update takes.  `init`: the run starts from a noised clip.  Everything
         the class does not build fails here: eta is DDIM's option, NotImplementedError from every other class."""
         raise NotImplementedError
@@ -236,7 +240,36 @@ class DDIMScheduler(_AlphaScheduler):
         return SimpleNamespace(prev_sample=sap * x0 + s1ap * eps, pred_original_sample=x0)
 
 
-class DPMSolverMultistepScheduler(_Scheduler):
+class _LambdaScheduler(_Scheduler):
+    """DPM-Solver++ and UniPC: exponential integrators on lambda = -log sigma over the clamped sigma table, in the
+    variance-preserving frame - sigmas = table[timesteps] + [the final sigma], the noise level of a step index read from
+    them.  A subclass has `_reset` (the state of its `step()`)."""
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        T = self.config.num_train_timesteps
+        self.num_inference_steps = num_inference_steps
+        self.timesteps = torch.from_numpy(_trailing(T, num_inference_steps, np.int64))
+        sig = self.sigma_table[self.timesteps]
+        last = torch.zeros(1) if self.config.final_sigmas_type == "zero" else self.sigma_table[:1]
+        self.sigmas = torch.cat([sig, last]).to(torch.float32)
+        self._reset()
+
+    def noise_coefficients(self, j):
+        """(a_j, s_j) = (alpha_t, sigma_t) of sigmas[j], the level the latents have at step index j (j = number of
+        steps: the final sigma).  Float64 arithmetic on the float32 sigmas."""
+        self._check_index(j, closed=True)
+        return _vp(float(self.sigmas[j]))
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' DPMSolverMultistepScheduler.add_noise (UniPCMultistepScheduler's is the same): alpha_t x0 + sigma_t
+        noise at the schedule's own timesteps (one, or one per sample of the batch)."""
+        pairs = [self.noise_coefficients(self._index_of(t)) for t in _timestep_list(timesteps)]
+        a = _per_sample([p[0] for p in pairs], original_samples)
+        s = _per_sample([p[1] for p in pairs], original_samples)
+        return a * original_samples + s * noise
+
+
+class DPMSolverMultistepScheduler(_LambdaScheduler):
     """DPM-Solver++ (multistep, data prediction, midpoint) for the zero-terminal-SNR v-prediction schedule: the arithmetic
     of diffusers==0.29.2 `DPMSolverMultistepScheduler` restated for the options listed in `__init__` (any other value
     raises NotImplementedError naming the option).
@@ -284,15 +317,6 @@ class DPMSolverMultistepScheduler(_Scheduler):
         self._x0_prev = None
         self._taken = 0
 
-    def set_timesteps(self, num_inference_steps, device=None):
-        T = self.config.num_train_timesteps
-        self.num_inference_steps = num_inference_steps
-        self.timesteps = torch.from_numpy(_trailing(T, num_inference_steps, np.int64))
-        sig = self.sigma_table[self.timesteps]
-        last = torch.zeros(1) if self.config.final_sigmas_type == "zero" else self.sigma_table[:1]
-        self.sigmas = torch.cat([sig, last]).to(torch.float32)
-        self._reset()
-
     def solver_order_at(self, i, begin_index=0):
         """Order of the update at step index i of a run that started at `begin_index` (diffusers' step(): first order
         at the first step of a run, at solver_order 1, and at the last step under final_sigmas_type "zero",
@@ -327,20 +351,6 @@ class DPMSolverMultistepScheduler(_Scheduler):
         self._no_eta(eta)
         return "multistep", [self.multistep_coefficients(begin_index + i, begin_index) for i in range(len(timesteps))]
 
-    def noise_coefficients(self, j):
-        """(a_j, s_j) = (alpha_t, sigma_t) of sigmas[j], the level the latents have at step index j (j = number of
-        steps: the final sigma).  Float64 arithmetic on the float32 sigmas."""
-        self._check_index(j, closed=True)
-        return _vp(float(self.sigmas[j]))
-
-    def add_noise(self, original_samples, noise, timesteps):
-        """diffusers' DPMSolverMultistepScheduler.add_noise: alpha_t x0 + sigma_t noise at the schedule's own timesteps
-        (one, or one per sample of the batch)."""
-        pairs = [self.noise_coefficients(self._index_of(t)) for t in _timestep_list(timesteps)]
-        a = _per_sample([p[0] for p in pairs], original_samples)
-        s = _per_sample([p[1] for p in pairs], original_samples)
-        return a * original_samples + s * noise
-
     def step(self, model_output, timestep, sample, return_dict=True, **unused):
         """One update on tensors (v-prediction `model_output`), keeping the step index and the last x0 like diffusers."""
         if self.step_index is None:
@@ -355,6 +365,171 @@ class DPMSolverMultistepScheduler(_Scheduler):
         self.step_index += 1
         self._taken += 1
         out = SimpleNamespace(prev_sample=prev, pred_original_sample=x0)
+        return out if return_dict else (prev,)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# UniPC: per frame and timestep the corrector of the step that ended at the sample the UNet just saw, then the predictor
+# from the corrected sample, both linear in the data predictions m:
+#     m = a_i x - s_i v;   xc = q_s saved + q_m m + q_1 H[h1] + q_2 H[h2] + q_3 H[h3] if use_c else x
+#     out = k_x xc + k_m m + k_1 H[h1] + k_2 H[h2];   saved <- xc;   H[h_write] <- m
+# over the latents x, the window-averaged model output v, three per-frame history tensors H (a ring of three slots holding
+# the earlier m, newest in h1) and the saved corrected sample.  The fused `vx_overlap_unipc_step` kernel runs it, fed by
+# `UniPCMultistepScheduler.unipc_coefficients(i, begin_index)`.
+UniPCStep = collections.namedtuple("UniPCStep", "h1 h2 h3 h_write use_c a_i s_i q_s q_m q_1 q_2 q_3 k_x k_m k_1 k_2")
+UniPCStep.__doc__ = """Coefficients of one UniPC update: history slots read (h1..h3: the data predictions of the previous
+three steps, newest first) and written (h_write), each 0..2 or -1 (none); use_c 1 (the corrector runs from the saved
+sample) or 0 (xc = x); m = a_i x - s_i v; xc = q_s saved + q_m m + sum_j q_j H[h_j]; out = k_x xc + k_m m + k_1 H[h1] +
+k_2 H[h2]; the sample saved is xc, the history entry written is m."""
+
+
+class UniPCMultistepScheduler(_LambdaScheduler):
+    """UniPC (unified predictor-corrector, Zhao et al. 2023; multistep, data prediction) for the zero-terminal-SNR
+    v-prediction schedule: the arithmetic of diffusers==0.29.2 `UniPCMultistepScheduler` restated for the options listed in
+    `__init__` (any other value raises NotImplementedError naming the option).  Timesteps, sigmas and noise levels are
+    DPMSolverMultistepScheduler's (the 2^-24 clamp included); the loop's frame is variance-preserving.
+
+    With lambda = -log sigma, a step of order p from point a to point b (h = lambda_b - lambda_a, hh = -h) over the base
+    sample x_a, the data prediction m0 at a and older ones m_k at r_k = (lambda_k - lambda_a) / h is
+        x_b = (s_b / s_a) x_a - alpha_b phi1 m0 - alpha_b B (sum_k rho_k (m_k - m0) / r_k [+ rho_p (m_t - m0)])
+    with phi1 = expm1(hh), B = hh ("bh1") or phi1 ("bh2"), and rho the solution of R rho = b (R[i][k] = r_k^(i-1), r_p = 1,
+    b_i = g_i i! / B) - the whole system for the corrector, whose last unknown weighs the prediction m_t at b itself; its
+    leading (p-1) x (p-1) block for the predictor; the published shortcut rho = [0.5] for the second-order predictor and
+    the first-order corrector.  After every UNet evaluation the step that ended there is corrected with the new m_t (no
+    further evaluation), then the predictor runs from the corrected sample - `unipc_coefficients(i)` folds both into the
+    coefficients of the fused `vx_overlap_unipc_step` kernel.  `step()` is the stateful diffusers-style tensor API."""
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False,
+                 dynamic_thresholding_ratio=0.995, sample_max_value=1.0, predict_x0=True, solver_type="bh2",
+                 lower_order_final=True, disable_corrector=(), solver_p=None, use_karras_sigmas=False,
+                 timestep_spacing="linspace", steps_offset=0, final_sigmas_type="zero", rescale_betas_zero_snr=False,
+                 **unused):
+        # (clip_sample, set_alpha_to_one, ... of a DDIM configuration are not parameters of this solver: ignored, as
+        # diffusers' from_config does)
+        disable_corrector = [] if disable_corrector is None else list(disable_corrector)
+        self._check_options(("trained_betas", trained_betas, trained_betas is None),
+                            ("solver_order", solver_order, solver_order in (1, 2, 3)),
+                            ("prediction_type", prediction_type, prediction_type == "v_prediction"),
+                            ("thresholding", thresholding, not thresholding),
+                            ("predict_x0", predict_x0, predict_x0 is True),
+                            ("solver_type", solver_type, solver_type in ("bh1", "bh2")),
+                            ("lower_order_final", lower_order_final, lower_order_final is True),
+                            ("disable_corrector", disable_corrector,
+                             all(isinstance(k, int) and not isinstance(k, bool) for k in disable_corrector)),
+                            ("solver_p", solver_p, solver_p is None),
+                            ("use_karras_sigmas", use_karras_sigmas, not use_karras_sigmas),
+                            ("final_sigmas_type", final_sigmas_type, final_sigmas_type in ("zero", "sigma_min")),
+                            ("timestep_spacing", timestep_spacing, timestep_spacing == "trailing"))
+        self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                                      beta_schedule=beta_schedule, solver_order=solver_order,
+                                      prediction_type=prediction_type, predict_x0=predict_x0, solver_type=solver_type,
+                                      lower_order_final=lower_order_final, disable_corrector=disable_corrector,
+                                      solver_p=solver_p, final_sigmas_type=final_sigmas_type,
+                                      timestep_spacing=timestep_spacing, steps_offset=steps_offset,
+                                      rescale_betas_zero_snr=rescale_betas_zero_snr)
+        self._tables(sigma=True)
+        self.timesteps = None
+        self.sigmas = None
+        self._reset()
+
+    def _reset(self):
+        self.step_index = None
+        self._ring = [None] * 3
+        self._saved = None
+        self._taken = 0
+
+    def solver_order_at(self, i, begin_index=0):
+        """p_i = min(solver_order, n - i, i - begin_index + 1): the order of the predictor of step index i in a run that
+        started at `begin_index` - and of the corrector that redoes that step at index i + 1 (diffusers' this_order under
+        lower_order_final; the history starts empty at begin_index)."""
+        self._check_index(i, begin_index)
+        return min(self.config.solver_order, self.num_inference_steps - i, i - begin_index + 1)
+
+    def _bh_weights(self, a, order, corrector):
+        """(c_x, c_0, [c_1 .. c_{order-1}], c_t) of the step from point a to point a + 1 written
+        x_b = c_x x_a + c_0 m0 + sum_k c_k m_k + c_t m_t, m_k the data prediction at point a - k (c_t = 0 for the
+        predictor): the (m_k - m0) / r_k differences folded into the coefficients.  Float64 arithmetic on the float32
+        sigmas; a predictor step that ends at sigma = 0 (first order by solver_order_at) is m0 itself."""
+        sg = self.sigmas
+        s_a, s_b = float(sg[a]), float(sg[a + 1])
+        if s_b == 0.0:
+            return 0.0, 1.0, [], 0.0
+        (al_b, sd_b), (_, sd_a) = _vp(s_b), _vp(s_a)
+        lam_a = -math.log(s_a)
+        h = -math.log(s_b) - lam_a
+        hh = -h
+        rks = [(-math.log(float(sg[a - k])) - lam_a) / h for k in range(1, order)] + [1.0]
+        phi1 = math.expm1(hh)
+        B = hh if self.config.solver_type == "bh1" else phi1
+        g, fact, b = phi1 / hh - 1.0, 1, []
+        for i in range(1, order + 1):
+            b.append(g * fact / B)
+            fact *= i + 1
+            g = g / hh - 1.0 / fact
+        R = [[rk ** (i - 1) for rk in rks] for i in range(1, order + 1)]
+        if corrector:
+            rho = [0.5] if order == 1 else np.linalg.solve(np.array(R), np.array(b)).tolist()
+        elif order <= 2:
+            rho = [0.5] * (order - 1)
+        else:
+            rho = np.linalg.solve(np.array(R)[:-1, :-1], np.array(b)[:-1]).tolist()
+        older = [-al_b * B * rho[k] / rks[k] for k in range(order - 1)]
+        rho_t = rho[order - 1] if corrector else 0.0
+        c_0 = -al_b * phi1 + al_b * B * (sum(rho[k] / rks[k] for k in range(order - 1)) + rho_t)
+        return sd_b / sd_a, c_0, older, -al_b * B * rho_t
+
+    def unipc_coefficients(self, i, begin_index=0):
+        """UniPCStep of step index i of a run that started at `begin_index`: the corrector from point i - 1 to i (order
+        p_{i-1}, base the saved sample; not at the first step of a run, nor when i - 1 is in disable_corrector, nor before
+        a predictor that ends at sigma = 0 and returns m whatever xc is) and the predictor from i to i + 1 (order p_i).
+        The data prediction of point j lives in ring slot (j - begin_index) % 3; this step's goes to the slot of point
+        i - 3, which a third-order corrector reads in the same update."""
+        p = self.solver_order_at(i, begin_index)
+        a_i, s_i = _vp(float(self.sigmas[i]))
+        k_x, k_m, k_old, _ = self._bh_weights(i, p, corrector=False)
+        r = i - begin_index
+        use_c = r > 0 and (i - 1) not in self.config.disable_corrector and float(self.sigmas[i + 1]) != 0.0
+        q_s = q_m = 0.0
+        q_old, pc = [], 0
+        if use_c:
+            pc = self.solver_order_at(i - 1, begin_index)
+            q_s, q_0, older, q_m = self._bh_weights(i - 1, pc, corrector=True)
+            q_old = [q_0] + older                      # m_{i-1} is the corrector's m0
+        reads = max(pc, len(k_old))
+        slots = [(r - j) % 3 if j <= reads else -1 for j in (1, 2)] + [(r - 3) % 3 if pc == 3 else -1]
+        q_old = q_old + [0.0] * (3 - len(q_old))
+        k_old = k_old + [0.0] * (2 - len(k_old))
+        return UniPCStep(*slots, r % 3, int(use_c), a_i, s_i, float(q_s), float(q_m), *map(float, q_old), float(k_x),
+                         float(k_m), *map(float, k_old))
+
+    def loop_steps(self, timesteps, begin_index, eta=0.0, init=False):
+        self._no_eta(eta)
+        return "unipc", [self.unipc_coefficients(begin_index + i, begin_index) for i in range(len(timesteps))]
+
+    def step(self, model_output, timestep, sample, return_dict=True, **unused):
+        """One update on tensors (v-prediction `model_output`), keeping the step index, the last data predictions and the
+        corrected sample like diffusers."""
+        if self.step_index is None:
+            self.step_index = self._index_of(int(timestep))
+        i = self.step_index
+        cf = self.unipc_coefficients(i, begin_index=i - self._taken)
+        H = self._ring
+        m = cf.a_i * sample - cf.s_i * model_output
+        xc = sample
+        if cf.use_c:
+            xc = cf.q_s * self._saved + cf.q_m * m
+            for slot, q in ((cf.h1, cf.q_1), (cf.h2, cf.q_2), (cf.h3, cf.q_3)):
+                if slot >= 0:
+                    xc = xc + q * H[slot]
+        prev = cf.k_x * xc + cf.k_m * m
+        for slot, k in ((cf.h1, cf.k_1), (cf.h2, cf.k_2)):
+            if slot >= 0:
+                prev = prev + k * H[slot]
+        self._saved, H[cf.h_write] = xc, m
+        self.step_index += 1
+        self._taken += 1
+        out = SimpleNamespace(prev_sample=prev, pred_original_sample=m)
         return out if return_dict else (prev,)
 
 
