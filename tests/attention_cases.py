@@ -138,7 +138,13 @@ def _m_tail4_masked(q, kb, vb, idx, k, v, kw):
     return kb, vb, dict(kw, masked=tuple(range(max(0, n - 4), n)))
 
 
+def _m_v_is_k(q, kb, vb, idx, k, v, kw):
+    return kb, kb, kw
+
+
 MUTANTS = {
+    # (vx_small_kv_attention: K and V are column halves of one buffer and V starts v_off columns in)
+    "V read at v_off = 0: the K columns": _mutant(_m_v_is_k),
     "extra zero-logit zero-value key": _mutant(_m_extra_zero_key),
     "last key counted twice": _mutant(_m_last_key_twice),
     "last key dropped": _mutant(_m_last_key_dropped),
@@ -429,7 +435,7 @@ ATTN_HEAD_DIMS = (8, 40, 64, 80, 160)           # 8 heads, batch 4, q_per_kv 2: 
 TEMPORAL_F = (1, 2, 15, 16, 17, 24, 31, 32)
 TEMPORAL_HEAD_DIMS = (8, 40, 80, 160)           # hw = 5, b = 2, 8 heads
 SMALL_KV_N_KV = (1, 5, 15, 16)
-SMALL_KV_HEAD_DIMS = (8, 40, 160)
+SMALL_KV_HEAD_DIMS = (8, 40, 64, 160)           # (64: its own shapes, `small_kv_geoms`)
 SMALL_KV_N_Q = (7, 100)                         # batch 3
 
 
@@ -450,4 +456,6 @@ def small_kv_heads(d, n_kv):
 
 
 def small_kv_geoms(d):
+    if d == 64:     # AudioProjection's shape: 16 heads, 61,440 and 65,536 of the 65,536 bytes of LDS the entry point admits
+        return [Geom(3, 16, n_q, n_kv, 64, 1) for n_kv in (15, 16) for n_q in (5, 100)]
     return [Geom(3, small_kv_heads(d, n_kv), n_q, n_kv, d, 1) for n_kv in SMALL_KV_N_KV for n_q in SMALL_KV_N_Q]

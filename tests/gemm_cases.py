@@ -40,6 +40,11 @@ Cases (every output is compared with `==`: bit-equal up to the sign of zero, unl
               these launches too, their statistics under the same rule.
 
 `MUTANTS` edit the REFERENCE (never a kernel); `EMULATIONS` are legitimate designs (float32 accumulation in another order).
+
+ROUTES["small conv"] holds the small-channel convolutions of the keypoint guider and the VAE encoder (cin in {8, 16, 32, 96} into
+n in {16, 32, 96}, cin 128 into 8, cin 256 into 320; pad 1, stride 1 and 2), where a 64-wide K tile holds several taps or parts
+of two; two mutants are theirs: a straddling tile that reads its later tap from the neighbouring pixel, and a last column
+without the zero fill.  The prologue's other routes (overlapping rows, GELU, the positional conv) are tests/prologue_cases.py.
 """
 from dataclasses import dataclass, field, replace
 from typing import Optional
@@ -202,6 +207,18 @@ def centre_tap_on_last_column(g, ox):
     return (ox * g.stride - g.lpad + g.kk // 2) >> g.ups == g.w - 1
 
 
+def straddling_tile(g):
+    """Index of the first 64-wide K tile that holds channels of two taps (-1: none, the taps end on tile boundaries)."""
+    if g.kk == 1 or g.cin % 64 == 0:
+        return -1
+    return next(t for t in range(-(-g.k // 64)) if (t * 64) // g.cin != (min(g.k, t * 64 + 64) - 1) // g.cin)
+
+
+def right_of_last_column(g, ox):
+    """Whether the output column's last tap lies one pixel right of the (upsampled) image."""
+    return ox * g.stride - g.lpad + g.kk - 1 >= (g.w << g.ups)
+
+
 def gather(g, dens, rows, mut=None, ks=None):
     """The im2col rows `rows` (int64 tensor) in float64 [R, K] (or the K indices `ks` of them): what the kernel's addressing
     must read, zero outside the image.  mut: one of the addressing mutants, applied where it bites among these rows."""
@@ -228,6 +245,13 @@ def gather(g, dens, rows, mut=None, ks=None):
         valid = valid | (hit[:, None] & (tap == (g.kk - 1) * g.kk + g.kk // 2)[None, :])
     elif mut == "second source first":
         ch = torch.where(ch < g.c2, ch + g.c1, ch - g.c2)
+    elif mut == "straddling K tile reads its second tap one pixel to the right":
+        # the first 64-wide K tile that holds two taps: the channels of its later tap(s) come from the neighbouring pixel
+        k0 = straddling_tile(g) * 64
+        lin = lin + ((ks >= k0) & (ks < k0 + 64) & (tap != k0 // g.cin))[None, :].to(I64)
+    elif mut == "no zero fill right of the last column":
+        # frame 0: the taps one pixel right of the image read what lies there in memory, the next row's first pixel
+        valid = valid | ((f == 0)[:, None] & (ux == we) & (uy >= 0) & (uy < he))
     lin = lin.clamp(0, g.nb * g.h * g.w - 1)
     ff, rem = lin // (g.h * g.w), lin % (g.h * g.w)
     return a_value(ff, rem // g.w, rem % g.w, ch[None, :], dens) * valid
@@ -512,6 +536,11 @@ def _mutate_acc(case, acc, mut, dev):
             rows = torch.tensor([(g.nb - 1) * oh * ow], dtype=I64, device=dev)
         elif mut == "tap crosses into the next frame":
             rows = torch.tensor([(oh - 1) * ow + ow // 2], dtype=I64, device=dev)
+        elif mut == "no zero fill right of the last column":
+            rows = torch.arange(0, oh * ow, dtype=I64, device=dev)
+            rows = rows[right_of_last_column(g, out_coords(g, rows)[2])]
+        elif mut == "straddling K tile reads its second tap one pixel to the right":
+            rows = torch.arange(0, min(oh * ow, 64), dtype=I64, device=dev)
         else:
             rows = torch.arange(0, min(16, g.m), dtype=I64, device=dev)
         for r0 in range(0, len(rows), 256):
@@ -522,7 +551,8 @@ def _mutate_acc(case, acc, mut, dev):
 
 ACC_MUTANTS = ("last K-term dropped in a 16-row band", "tap vector from the pixel to the right", "corner tap wraps",
                "tap crosses into the next frame", "one K-term dropped for one pixel of one frame",
-               "one K-term at the split boundary counted twice", "second source first", "grouped weights use group 0")
+               "one K-term at the split boundary counted twice", "second source first", "grouped weights use group 0",
+               "straddling K tile reads its second tap one pixel to the right", "no zero fill right of the last column")
 
 # name -> whether the mutant can differ from the reference at a geometry (a structural fact, never read off the outputs)
 MUTANTS = {
@@ -546,6 +576,11 @@ MUTANTS = {
     "last token dropped from V^T": lambda g: g.epi == "split" and g.seq_len > 0,
     "statistics of the unrounded accumulators": lambda g: bool(g.gn_hw or g.stats2),
     "grouped weights use group 0": lambda g: g.groups > 1,
+    # the small-channel convolutions (cin % 64 != 0: a 64-wide K tile holds several taps or parts of two)
+    "straddling K tile reads its second tap one pixel to the right": lambda g: straddling_tile(g) >= 0,
+    # the kernel's own zero fill (pad > 0; a bordered image brings its zeros along), where a tap reaches past the last column
+    "no zero fill right of the last column": lambda g: g.pad > 0 and g.h > 1 and bool(
+        right_of_last_column(g, torch.arange(g.out_hw[1])).any()),
 }
 
 
@@ -839,6 +874,14 @@ def _routes():
                  Launch(conv(2, 8, 6, 64, 160, bordered=True), _k(T64)),
                  Launch(conv(2, 8, 6, 64, 64, stride=2, pad_end=1), s64),
                  Launch(conv(2, 10, 8, 64, 160, window=(1, 2, 6, 4)), _k(T64))]
+    # the small-channel convolutions of the keypoint guider and the VAE encoder, 2 frames of 9 x 7, pad 1 (the gather's own zero
+    # fill), stride 1 and 2: a 64-wide K tile holds eight taps (cin 8), four (16), two (32), or two thirds of one and a third
+    # of the next (96: tiles 1, 2, 4, 5, ... straddle a tap boundary); n <= 32 on the 256 x 32 tile, n = 96 on 128 x 128
+    g32, g128 = _k(T256x32, addr="gather"), _k(T128, addr="gather")
+    r["small conv"] = [Launch(conv(2, 9, 7, cin, n, pad=1, stride=s), g32 if n <= 32 else g128)
+                       for cin in (8, 16, 32, 96) for n in (16, 32, 96) for s in (1, 2)] + \
+        [Launch(conv(2, 9, 7, 128, 8, pad=1, stride=s), g32) for s in (1, 2)] + \
+        [Launch(conv(2, 9, 7, 256, 320, pad=1, stride=s), g160) for s in (1, 2)]
     # classic split-K: the 8x8 level from K = 2560 on (ops._splitk: 8 slices); no folded LayerNorm there
     r["split-K"] = [Launch(conv(2, 8, 8, 320, 320, bordered=True), _k(T64, extra=",splitk8"), skip=("folded",)),
                     Launch(linear(128, 320, 2560), _k(T64, extra=",splitk8"), frame_rows=(64, None), skip=("folded",)),

@@ -108,7 +108,7 @@ def test_every_mutant_is_caught(route, capsys):
 def test_every_mutant_applies_somewhere():
     geos = [G.reduced(l.geo) for ls in G.ROUTES.values() for l in ls]
     idle = [m for m, applies in G.MUTANTS.items() if not any(applies(g) for g in geos)]
-    assert not idle and len(G.MUTANTS) == 17, idle
+    assert not idle and len(G.MUTANTS) == 19, idle
 
 
 def test_operands_are_functions_of_their_coordinates():

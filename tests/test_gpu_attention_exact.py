@@ -26,7 +26,8 @@ Routes (the kernel vx_last_kernel() names is asserted after every call), key til
       d = 512 with one head, one batch, n_kv in {65, 100}.
   vx_temporal_attention   f in {1, 2, 15, 16, 17, 24, 31, 32} x d in {8, 40, 80, 160}, hw = 5, b = 2, 8 heads.
   vx_small_kv_attention   n_kv in {1, 5, 15, 16} x d in {8, 40, 160} x n_q in {7, 100}, batch 3 (one kernel: nothing to route,
-      and the entry point does not set vx_last_kernel).
+      and the entry point does not set vx_last_kernel); d = 64 with 16 heads, AudioProjection's shape: n_kv in {15, 16} x n_q
+      in {5, 100} - 61,440 and 65,536 of the 65,536 bytes of LDS the entry point admits.
 """
 import pytest
 import torch
