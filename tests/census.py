@@ -18,13 +18,16 @@ last - then the real op runs on the original arguments and its result is returne
 and the post-call value of every tensor argument are compared with the restatement's, per op, at the bound of that op's
 own test in test_gpu_kernels.py (BOUNDS).  With GemmProfile / OpProfile active the kernel instantiations a call launched
 are attributed to it; `coverage_errors()` then lists every instantiation the region launched that no checked call did,
-every wrapped op called but never checked, and every `ops` entry point called that has no restatement."""
+every wrapped op called but never checked, and every `ops` entry point called that has no restatement.
+Row statistics a checked call consumes (`ln=`, `stats=`) are compared with float64 statistics of the rows they describe
+(tests/stats_spy.py, STAT_BOUNDS): a producer that skipped `stats_out` shows as a stale consumption, detail "fresh:..."."""
 import inspect
 from contextlib import contextmanager
 
 import torch
 
 import fake_ops
+import stats_spy
 
 # ---------------------------------------------------------------------------------------------------------- bounds
 # (relative L2, max|err| / max|ref|) per op, each the bound of that op's existing test in test_gpu_kernels.py.  Variants:
@@ -274,6 +277,9 @@ class Census:
             fa["fold"] = hit[1]
             self.checked_sigs.add(hit[2])
             self.checked_syms.update(hit[3])
+        # row statistics the launch is about to consume: they must describe the rows it normalises AS THEY ARE NOW
+        # (tests/stats_spy.py; the restatement below applies whatever statistics it is handed)
+        fresh = stats_spy.consumed(name, bound_real, self.fakes)
         ref = fake(*bound_fake.args, **bound_fake.kwargs)
         ref = _clone(ref, {}) if not isinstance(ref, tuple) else tuple(_clone(r, {}) for r in ref)
         got = self._run(real, a, k)
@@ -282,7 +288,7 @@ class Census:
         self.checked_syms.update(syms)
         self.checked_sigs.add((name, row.sig))
         # ---- comparisons
-        results = []
+        results = [] if fresh is None else [("fresh:" + fresh[0], (fresh[1], 0.0, 0))]
         arg_out = "out" if _is_t(bound_real.get("out")) else MAIN_OUT.get(name) if name in MAIN_OUT else \
             "h" if name == "audio_xattn" else None
         key = name + ("+ln" if bound_real.get("ln") is not None and name in ("gemm", "geglu", "gemm_split") else "") + \

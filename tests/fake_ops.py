@@ -244,7 +244,8 @@ def geglu(a, w_interleaved, bias_interleaved, out=None, ln=None):
 
 
 def ff_fused(h, w1_folded, b1, colsum, stats, w2, b2):
-    """vx_ff_fused = the two launches it replaces, in place on h (the kernel is bit-identical to them on the GPU)."""
+    """vx_ff_fused = the two launches it replaces, in place on h (on the GPU the kernel has their bits where they run on the
+    256-row tile it restates - frames of 256 rows and more; tests/test_gpu_block_wiring.py)."""
     g = geglu(h, w1_folded, b1, ln=(stats, colsum))
     return gemm(g, w2, b2, residual=h, out=h)
 
