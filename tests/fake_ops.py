@@ -173,7 +173,9 @@ def _conv_rows(a, a2, w, geom):
     img = F.pad(img, (geom.pad, max(need_w - geom.pad, 0), geom.pad, max(need_h - geom.pad, 0)))
     wt = w.double().view(n, geom.kh, geom.kw, c).permute(0, 3, 1, 2)
     y = F.conv2d(img, wt, stride=geom.stride)[:, :, :geom.h_out, :geom.w_out]
-    return y.permute(0, 2, 3, 1).reshape(geom.m, n)
+    # (contiguous like the kernel's output: for ONE frame the reshape is a column-major view, which every later elementwise
+    # step and `.clone()` would keep)
+    return y.permute(0, 2, 3, 1).reshape(geom.m, n).contiguous()
 
 
 def gemm(a, w, bias=None, *, geom=None, a2=None, residual=None, alpha=1.0, act=0, rowbias=None, rows_per_group=0,

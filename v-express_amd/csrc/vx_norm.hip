@@ -340,6 +340,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
                                                         const float* __restrict__ beta,
                                                         const float* __restrict__ add, int add_rows_per_entry,
                                                         int add_entries, bf16_t* __restrict__ out, int ldo) {
+  // A row's bits must not depend on which of the LN_R slots of a wave pass it sits in (a frame computed alone = its rows of
+  // the batched call).  With contraction left to the compiler the unrolled slots came out as a mix of fused (v_pk_fma_f32)
+  // and unfused (v_pk_mul_f32 + v_pk_add_f32) multiply-adds, slot by slot: every product and sum is rounded on its own here.
+#pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int nwaves = gridDim.x * 4;
