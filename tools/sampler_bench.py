@@ -10,6 +10,7 @@ with a chosen sampler and step count (GPU box):
     python tools/sampler_bench.py --scheduler ddim --steps 25 --init-video --strength 0.6 --mask lower-half
     python tools/sampler_bench.py --scheduler ddim --steps 25 --audio-guidance-scale 6 [--guidance-scale 1]
     python tools/sampler_bench.py --scheduler ddim --steps 25 --apg-eta 0 --apg-norm-threshold 20 --apg-momentum -0.5
+    python tools/sampler_bench.py --scheduler ddim --steps 25 --guidance-refresh 2 [--guidance-reuse linear]
 Prints one JSON line: ms per clip (host clock around whole clips, ending in a device synchronise), the denoise and decode
 milliseconds of the same clips (HIP events), and the average microseconds of the per-step update launch (HIP events
 around each `ops.overlap_ddim_step` / `ops.overlap_multistep_step` / `ops.overlap_ancestral_step` /
@@ -30,6 +31,11 @@ window for s > 1, the rows (m, c) for s <= 1 < s_a); `combine3_us` / `rescale3_u
 routes above; not with --guidance-rescale): `apg_us` is then the two launches of one `ops.guidance_apg` call, a guided
 step's, timed like the update launch, and `apg_combine_us` the plain combine of the same rows (`ops.combine_units` /
 `ops.combine_units3` into a scratch buffer, right after every APG call of the same instrumented clip), for comparison.
+--guidance-refresh K [--guidance-reuse hold|linear] switches guidance reuse on (K > 1; with any row route, not with
+--guidance-rescale or --apg-eta): the line then carries `refresh_steps`, and from one instrumented clip `keep_us` (the
+`ops.combine_units_keep` launch of a refresh step), `reused_us` (the `ops.combine_reused` launch of a reuse step) and
+`keep_combine_us` (the plain combine of the same rows into a scratch buffer right after every keep launch of that clip:
+`ops.combine_units` / `ops.combine_units3`), each timed like the update launch.
 --frames F --context-frames f --context-overlap o --context-schedule uniform|uniform_fit choose the clip length and its
 windows (defaults: 16 frames in one window of 16, overlap 4, `uniform`); --overlap-blend mean|linear|pyramid the stitch of
 overlapping windows - a weighted blend adds one `ops.overlap_blend` launch per step (`overlap_blend_us`, timed like the
@@ -65,6 +71,9 @@ def main():
                     help="adaptive projected guidance: the scale of the part parallel to the conditional prediction")
     ap.add_argument("--apg-norm-threshold", type=float, default=0.0, help="cap of a guidance difference's norm per frame")
     ap.add_argument("--apg-momentum", type=float, default=0.0)
+    ap.add_argument("--guidance-refresh", type=int, default=1,
+                    help="guidance reuse: compute the guidance differences on every K-th guided step only")
+    ap.add_argument("--guidance-reuse", choices=("hold", "linear"), default="hold")
     ap.add_argument("--init-video", action="store_true", help="start from a synthetic init video (img2img)")
     ap.add_argument("--strength", type=float, default=1.0, help="run the last int(steps * strength) timesteps")
     ap.add_argument("--mask", choices=("none", "lower-half"), default="none",
@@ -161,6 +170,8 @@ def main():
         extra["overlap_blend"] = args.overlap_blend
     if args.apg_eta is not None:
         extra["apg"] = (args.apg_eta, args.apg_norm_threshold, args.apg_momentum)
+    if args.guidance_refresh != 1:
+        extra.update(guidance_refresh=args.guidance_refresh, guidance_reuse=args.guidance_reuse)
 
     def one_clip(ev=None):
         if ev:
@@ -243,6 +254,37 @@ def main():
             ops.guidance_apg = orig
         torch.cuda.synchronize()
         return [1e3 * sum(m[i][0].elapsed_time(m[i][1]) for m in marks) / max(len(marks), 1) for i in (0, 1)]
+
+    def reuse_launch_us():
+        """(the ops.combine_units_keep launch, the plain combine of the same rows, the ops.combine_reused launch),
+        microseconds: one instrumented clip in which every keep launch is followed by the combine into a scratch buffer."""
+        orig_keep, orig_reused, keeps, plains, reuseds = ops.combine_units_keep, ops.combine_reused, [], [], []
+
+        def timed(fn, marks):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            fn()
+            e.record()
+            marks.append((s, e))
+
+        def keep(gathered, uidx, c, f, hw, guidance, audio_guidance, diffs, preds):
+            timed(lambda: orig_keep(gathered, uidx, c, f, hw, guidance, audio_guidance, diffs, preds), keeps)
+            scratch = torch.empty_like(preds)
+            if uidx.shape[1] == 3:
+                timed(lambda: ops.combine_units3(gathered, uidx, c, f, hw, guidance, audio_guidance, scratch), plains)
+            else:
+                timed(lambda: ops.combine_units(gathered, uidx, c, f, hw, guidance, scratch), plains)
+
+        def reused(*a):
+            timed(lambda: orig_reused(*a), reuseds)
+        ops.combine_units_keep, ops.combine_reused = keep, reused
+        try:
+            one_clip()
+        finally:
+            ops.combine_units_keep, ops.combine_reused = orig_keep, orig_reused
+        torch.cuda.synchronize()
+        return [round(1e3 * sum(s.elapsed_time(e) for s, e in m) / len(m), 2) if m else None
+                for m in (keeps, plains, reuseds)]
     n_updates, update_us = update_launch_us(update)
     blend_launches, blend_us = update_launch_us("known_blend") if args.init_video else (0, None)
     wblend_launches, wblend_us = update_launch_us("overlap_blend") if args.overlap_blend != "mean" else (0, None)
@@ -251,15 +293,20 @@ def main():
     guided = pipe.last_guidance["guided_steps"]
     rows = pipe.last_guidance.get("rows")
     three = rows == ("u", "m", "c")
+    reusing = args.guidance_refresh != 1 and len(pipe.last_guidance.get("refresh_steps", ())) < guided
     rescaled = args.guidance_rescale > 0 and guided
     rescale_us = round(update_launch_us("guidance_rescale")[1], 2) if rescaled and not three else None
     rescale3_us = round(update_launch_us("guidance_rescale3")[1], 2) if rescaled and three else None
-    combine3_us = round(update_launch_us("combine_units3")[1], 2) if three and guided and not rescaled and args.apg_eta is None else None
+    combine3_us = round(update_launch_us("combine_units3")[1], 2) if three and guided and not rescaled and args.apg_eta is None and not reusing else None
     apg_us = apg_combine_us = None
     if args.apg_eta is not None and guided:
         apg_us, apg_combine_us = (round(v, 2) for v in apg_launch_us())
+    keep_us = keep_combine_us = reused_us = None
+    if reusing:
+        keep_us, keep_combine_us, reused_us = reuse_launch_us()
     combine_us = None
-    if (rescale_us is None and rescale3_us is None and combine3_us is None and apg_us is None) or guided < args.steps:
+    if (rescale_us is None and rescale3_us is None and combine3_us is None and apg_us is None and not reusing) \
+            or guided < args.steps:
         combine_us = round(update_launch_us("combine_units")[1], 2)
     ddim_us = None
     if update == "overlap_ancestral_step":
@@ -284,6 +331,9 @@ def main():
         guidance_end=args.guidance_end, guided_steps=guided, rescale_us=rescale_us, combine_us=combine_us,
         audio_guidance_scale=args.audio_guidance_scale, rows=rows, combine3_us=combine3_us, rescale3_us=rescale3_us,
         apg=pipe.last_guidance.get("apg"), apg_us=apg_us, apg_combine_us=apg_combine_us,
+        guidance_refresh=args.guidance_refresh, guidance_reuse=args.guidance_reuse if args.guidance_refresh != 1 else None,
+        refresh_steps=pipe.last_guidance.get("refresh_steps"), keep_us=keep_us, keep_combine_us=keep_combine_us,
+        reused_us=reused_us,
         clip_ms_min=round(min(per_clip), 2), clip_ms_max=round(max(per_clip), 2), init_video=args.init_video,
         strength=args.strength, mask=args.mask, begin_index=begin, steps_run=len(timesteps), encode_ms=encode_ms,
         blend_launches=blend_launches, blend_us=None if blend_us is None else round(blend_us, 2), postprocess=post,

@@ -1,7 +1,8 @@
 """Reader of the C ABI header include/vexpress_hip.h: the ABI version, the enum constants, the parameter structs and the
 prototypes, as ctypes types.  lib.py binds both libraries from it, so the header is the only statement of the contract.
-include/vexpress_hip_guidance.h, include/vexpress_hip_samplers.h and include/vexpress_hip_solvers.h, the second, third and
-fourth header (entry points added without touching the earlier ones), are read the same way.
+include/vexpress_hip_guidance.h, include/vexpress_hip_samplers.h, include/vexpress_hip_solvers.h and
+include/vexpress_hip_reuse.h, the second to fifth header (entry points added without touching the earlier ones), are read
+the same way.
 Pure Python: no torch, no shared library.  It fails closed: once comments, preprocessor lines, the extern "C" braces and
 every declaration it has understood are taken out, anything but whitespace left over is an ImportError naming it."""
 import collections
@@ -14,6 +15,7 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 GUIDANCE_HEADER = os.path.join(os.path.dirname(HEADER), "vexpress_hip_guidance.h")
 SAMPLERS_HEADER = os.path.join(os.path.dirname(HEADER), "vexpress_hip_samplers.h")
 SOLVERS_HEADER = os.path.join(os.path.dirname(HEADER), "vexpress_hip_solvers.h")
+REUSE_HEADER = os.path.join(os.path.dirname(HEADER), "vexpress_hip_reuse.h")
 
 # version: int; enums: {name: value}; structs: {C name: [(field, ctypes type, array length or 0)]}; classes: {C name: the
 # ctypes.Structure built from those fields}; functions: {name: (restype, [(parameter, ctypes type)])}, all in header order
@@ -124,3 +126,10 @@ def solvers_header():
     """include/vexpress_hip_solvers.h, parsed once per process (version macro VX_SOLVERS_ABI_VERSION)."""
     with open(SOLVERS_HEADER) as f:
         return parse(f.read(), SOLVERS_HEADER, "VX_SOLVERS_ABI_VERSION")
+
+
+@functools.lru_cache(maxsize=None)
+def reuse_header():
+    """include/vexpress_hip_reuse.h, parsed once per process (version macro VX_REUSE_ABI_VERSION)."""
+    with open(REUSE_HEADER) as f:
+        return parse(f.read(), REUSE_HEADER, "VX_REUSE_ABI_VERSION")

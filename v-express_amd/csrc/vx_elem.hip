@@ -2,6 +2,7 @@
 // UNet; they exist so that latents, predictions and the DDIM state never leave HBM (the reference round-trips
 // them through the host every window: pipelines/v_express_pipeline.py:521,538,572).
 #include "vx_common.h"
+#include "vx_guidance_mix.h"
 #include "vx_overlap.h"
 #include "vx_rng.h"
 #include "../../include/vexpress_hip.h"
@@ -105,23 +106,7 @@ __global__ void pack_rows_kernel(const float* __restrict__ src, int ld, long row
   dst[idx] = src[r * ld + ch];
 }
 
-// g = u + s (cnd - u), and for three-row guidance (a separate audio scale) g = u + s (m - u) + s_audio (c - m) over the rows
-// (u, m, c) of a window - u without any condition, m ("silent") with the reference bank and the keypoints but all-zero audio,
-// c with everything - evaluated as cfg_mix(u, m, s) + s_audio * (c - m): where c and m hold equal bits this is the two-row
-// u + s (m - u).
-__device__ __forceinline__ float cfg_mix(float u, float cnd, float guidance) { return u + guidance * (cnd - u); }
-
-__device__ __forceinline__ float cfg_mix3(float u, float m, float cnd, float guidance, float audio) {
-  return cfg_mix(u, m, guidance) + audio * (cnd - m);
-}
-
-// the guided prediction at one element of a window's rows: rows[0] = u, rows[ROWS - 1] = c, and rows[1] = m for ROWS = 3.
-// ROWS = 1 (no guidance) evaluates u + s (u - u) like the others: -0.0 comes out as +0.0 and an infinity as NaN
-template <int ROWS>
-__device__ __forceinline__ float guided_value(const float* const* rows, long i, float guidance, float audio) {
-  if constexpr (ROWS == 3) return cfg_mix3(rows[0][i], rows[1][i], rows[2][i], guidance, audio);
-  else return cfg_mix(rows[0][i], rows[ROWS - 1][i], guidance);
-}
+// cfg_mix / cfg_mix3 / guided_value, the guided prediction at one element of a window's rows: vx_guidance_mix.h
 
 // The all-gathered unit predictions [units_total, f_loc*hw, c] -> guided window predictions [nW, c, f, hw] in ONE launch
 // (replaces the per-slot copies + one cfg_combine per window).  unit_index: int32 [nW][ROWS][S] = index of the unit buffer

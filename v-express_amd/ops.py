@@ -1,5 +1,5 @@
 """Tensor-level wrappers around the C ABI (include/vexpress_hip.h, include/vexpress_hip_guidance.h,
-include/vexpress_hip_samplers.h, include/vexpress_hip_solvers.h).
+include/vexpress_hip_samplers.h, include/vexpress_hip_solvers.h, include/vexpress_hip_reuse.h).
 
 PyTorch is used for device memory and streams only: every wrapper passes raw device pointers, explicit
 shapes/strides and `torch.cuda.current_stream()` to libvexpress_hip.so.  Activations are bf16
@@ -1449,6 +1449,62 @@ def guidance_apg(gathered, unit_index, c, f, hw, guidance, audio_guidance, eta, 
                                  float(audio_guidance), eta, r, beta,
                                  _ptr(momentum_buf), _ptr(workspace),
                                  workspace.numel(), _ptr(preds), _stream()), "vx_guidance_apg")
+
+
+def _check_slots(name, what, slots, n, preds):
+    """A float32 buffer of `n` difference slots shaped like preds ([n, nW, c, f, hw]) of `combine_units_keep` /
+    `combine_reused`."""
+    if not isinstance(slots, torch.Tensor) or slots.dtype != torch.float32 or not slots.is_contiguous():
+        raise TypeError(f"{name}: contiguous float32 {what} expected")
+    if slots.numel() != n * preds.numel():
+        raise ValueError(f"{name}: {what} must hold [{n}, nW, c, f, hw] elements")
+
+
+def combine_units_keep(gathered, unit_index, c, f, hw, guidance, audio_guidance, diffs, preds):
+    """The combine of a guidance-refresh step (vx_combine_units_keep, include/vexpress_hip_reuse.h): gathered fp32
+    [units_total, (f/S)*hw, c]; unit_index int32 [nW, rows, S], rows = 2 ((u, c) or (m, c), guided by `guidance`) or 3
+    ((u, m, c): `guidance` on m - u, `audio_guidance` on c - m) -> preds fp32 [nW, c, f, hw] with the bits of
+    `combine_units` / `combine_units3`, and diffs fp32 [rows - 1, nW, c, f, hw] = (row k + 1) - (row k)."""
+    rows = unit_index.shape[1] if unit_index.dim() == 3 else 0
+    if rows not in (2, 3):
+        raise ValueError("combine_units_keep: unit_index must be [nW, 2, S] (the rows (u, c) or (m, c)) or [nW, 3, S] "
+                         "(the rows u, m, c of every window)")
+    nW, S = _check_units("combine_units_keep", rows, gathered, unit_index, c, f, hw, preds)
+    _check_slots("combine_units_keep", "diffs", diffs, rows - 1, preds)
+    L.check(_lib.vx_combine_units_keep(_ptr(gathered), _ptr(unit_index), nW, rows, S, c, f, hw, float(guidance),
+                                       float(audio_guidance), _ptr(diffs), _ptr(preds), _stream()),
+            "vx_combine_units_keep")
+
+
+def combine_reused(gathered, unit_index, c, f, hw, last, prev, a1, b1, a2, b2, preds):
+    """The combine of a guidance-reuse step (vx_combine_reused): gathered fp32 [units_total, (f/S)*hw, c]; unit_index
+    int32 [nW, 1, S], the conditional row alone; last, prev fp32 [n, nW, c, f, hw], n = 1 or 2: the differences stored at
+    the last refresh and at the one before it (prev: None if and only if b1 == b2 == 0) -> preds fp32 [nW, c, f, hw] =
+    c + a1 last[0] + b1 prev[0] + a2 last[1] + b2 prev[1], in that order, each operation rounded to float32 on its own."""
+    if unit_index.dim() != 3 or unit_index.shape[1] != 1:
+        raise ValueError("combine_reused: unit_index must be [nW, 1, S] (the conditional row of every window)")
+    nW, _, S = unit_index.shape
+    if unit_index.dtype != torch.int32 or not unit_index.is_contiguous() or not gathered.is_contiguous():
+        raise TypeError("combine_reused: contiguous int32 index / contiguous gathered buffer expected")
+    if gathered.dtype != torch.float32 or preds.dtype != torch.float32 or not preds.is_contiguous():
+        raise TypeError("combine_reused: contiguous float32 gathered / preds expected")
+    if f % S or gathered.numel() % ((f // S) * hw * c) or preds.numel() != nW * c * f * hw:
+        raise ValueError("combine_reused: buffer sizes do not match (nW, c, f, hw, S)")
+    if not isinstance(last, torch.Tensor) or last.numel() not in (preds.numel(), 2 * preds.numel()):
+        raise ValueError("combine_reused: last must hold [n, nW, c, f, hw] elements, n = 1 or 2")
+    n = last.numel() // preds.numel()
+    _check_slots("combine_reused", "last", last, n, preds)
+    a1, b1, a2, b2 = float(a1), float(b1), float(a2), float(b2)
+    if not all(math.isfinite(v) for v in (a1, b1, a2, b2)):
+        raise ValueError("combine_reused: a1, b1, a2, b2 must be finite")
+    if n == 1 and (a2 != 0.0 or b2 != 0.0):
+        raise ValueError("combine_reused: a2 and b2 must be 0 with one difference")
+    if (b1 != 0.0 or b2 != 0.0) != (prev is not None):
+        raise ValueError("combine_reused: prev must be given when b1 or b2 is not 0 and None when both are 0")
+    if prev is not None:
+        _check_slots("combine_reused", "prev", prev, n, preds)
+    L.check(_lib.vx_combine_reused(_ptr(gathered), _ptr(unit_index), nW, n, S, c, f, hw, _ptr(last), _ptr(prev), a1, b1,
+                                   a2, b2, _ptr(preds), _stream()), "vx_combine_reused")
 
 
 def overlap_ddim_step(latents, preds, terms, frame_ids, counts, coef):

@@ -20,6 +20,7 @@ transformers module.  The benchmark and the loop parity tests pass the prologue 
 from typing import Callable, List, Optional, Union
 
 import math
+import numbers
 import os
 
 import torch
@@ -30,7 +31,7 @@ from .context import blend_weights, check_blend, get_context_scheduler, overlap_
 from .distributed import (DistContext, MixedUnitSchedule, UnitSchedule, choose_frame_shards, choose_mixed_shards,
                           split_frames)
 from .mutual_self_attention import ReferenceAttentionControl
-from .sampling import GUIDANCE_ROWS, Guidance, Known, Sampler, Stitch, UnitCall, check_known
+from .sampling import GUIDANCE_ROWS, REUSE_MODES, Guidance, Known, Sampler, Stitch, UnitCall, check_known
 from .scheduler import _Scheduler
 
 
@@ -90,6 +91,25 @@ def check_apg(apg, guidance_rescale=0.0):
         raise ValueError("apg_eta together with guidance_rescale > 0: both fight the same defect (the over-driven guided "
                          "prediction), and the combination is not built; pass one of them")
     return eta, r, beta
+
+
+def check_reuse(guidance_refresh, guidance_reuse, guidance_rescale=0.0, apg=None):
+    """Validates the guidance-reuse controls; returns None for the period 1 (every guided step runs its rows, as without
+    the keywords) or (period, mode)."""
+    k = guidance_refresh
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or k < 1:
+        raise ValueError(f"guidance_refresh must be an integer >= 1, got {guidance_refresh!r}")
+    if guidance_reuse not in REUSE_MODES:
+        raise ValueError(f"guidance_reuse must be one of {REUSE_MODES}, got {guidance_reuse!r}")
+    if k == 1:
+        return None
+    if float(guidance_rescale) > 0.0:
+        raise ValueError("guidance_refresh > 1 together with guidance_rescale > 0: the rescale needs the row statistics of "
+                         "a full step, which a reuse step does not run, and the combination is not built; pass one of them")
+    if apg is not None and apg[0] is not None:
+        raise ValueError("guidance_refresh > 1 together with apg_eta: the projection needs the row statistics of a full "
+                         "step, which a reuse step does not run, and the combination is not built; pass one of them")
+    return int(k), guidance_reuse
 
 
 def check_audio_guidance(audio_guidance_scale):
@@ -188,7 +208,9 @@ class VExpressPipeline:
         # last one the last_schedule-style dict of the conditional-only plan of its unguided steps, or None.  A call that
         # passes audio_guidance_scale also finds `rows` (guidance_rows: ("u", "c"), ("u", "m", "c"), ("m", "c") or
         # ("c",)) and `audio_scale` in it; without the keyword the dict is what it was before the keyword existed.  A call
-        # that passes apg (apg_eta) finds `apg` = dict(eta, norm_threshold, momentum), or None where it was ignored
+        # that passes apg (apg_eta) finds `apg` = dict(eta, norm_threshold, momentum), or None where it was ignored.  A
+        # call with guidance_refresh > 1 finds `refresh` (the period), `reuse` ("hold" or "linear") and `refresh_steps`
+        # (the indices of the guided steps that ran all their rows; empty where the keywords were ignored)
         self.last_guidance = {}
         # init-video sampling of the last denoise() call: dict(begin_index, masked, blend_launches) - the step index the
         # loop started at, whether a latent mask was blended in after every step, and the vx_known_blend launches of the
@@ -437,7 +459,7 @@ class VExpressPipeline:
     def denoise(self, latents, kps_tokens, audio, timesteps, windows, guidance_scale, callback=None,
                 callback_steps=1, *, begin_index=None, eta=0.0, noise_seed=None, guidance_rescale=0.0,
                 guidance_start=0.0, guidance_end=1.0, known=None, audio_guidance_scale=None, overlap_blend="mean",
-                apg=None):
+                apg=None, guidance_refresh=1, guidance_reuse="hold"):
         """pipelines/v_express_pipeline.py:526-583.  latents fp32 [1,4,F,h,w] (device, updated in place);
         kps_tokens bf16 [b, F, hw, C0]; audio bf16 [b, F, n_ctx, 768] with b = 2 (uncond, cond) under classifier-free
         guidance (guidance_scale > 1, :443) and b = 1 (the conditional row only) without.
@@ -469,6 +491,13 @@ class VExpressPipeline:
         step), is capped at the norm norm_threshold (0: no cap) and has its part parallel to the conditional prediction
         scaled by eta (Sadat et al., diffusers' AdaptiveProjectedGuidance, on the model output).  Not together with
         guidance_rescale; an unguided step neither reads nor advances the buffers; ignored without guidance.
+        Guidance reuse: guidance_refresh = k > 1 runs all rows of a guided step only on the refresh steps - the first
+        and the last guided step and every k-th between (sampling.refresh_roles) - where vx_combine_units_keep forms the
+        prediction of the plain combine, bit for bit, and stores the differences of consecutive rows; the guided steps
+        between run the conditional row alone, on the unit plan of an unguided step, and vx_combine_reused adds the stored
+        differences: c + sum (s_k - 1) L_k with guidance_reuse = "hold", and with "linear" the differences of the last two
+        refreshes extrapolated in the step index (hold until there are two).  Everything after the prediction is
+        unchanged.  Not together with guidance_rescale or apg; ignored without guidance; k = 1 is the loop without it.
         Init-video sampling (every sampler): known = (init, noise, m) - the clip's clean latents and the N(0,1) tensor,
         fp32 shaped like `latents`, and the latent mask fp32 [F, h*w] in [0, 1] (1 = regenerate, 0 = keep) or None.  The
         loop then starts from a_b init + s_b noise, b = begin_index (what `latents` held is not read), with (a_j, s_j)
@@ -490,6 +519,7 @@ class VExpressPipeline:
         guidance_rescale, guided = check_guidance(guidance_rescale, guidance_start, guidance_end, len(timesteps))
         row_names = guidance_rows(guidance_scale, audio_guidance_scale)
         apg = check_apg(apg, guidance_rescale)
+        reuse = check_reuse(guidance_refresh, guidance_reuse, guidance_rescale, apg)
         init, noise, kmask = check_known(known, latents)
         if update != "ddim" or known is not None:
             all_ts = [int(t) for t in self.scheduler.timesteps.tolist()]
@@ -518,7 +548,7 @@ class VExpressPipeline:
         guidance = Guidance(row_names, guidance_scale, audio_guidance_scale, guidance_rescale, guided, kps_tokens, audio,
                             lambda audio_is_zero, half_rows: self._unit_plan(latents, kps_tokens, audio, audio_is_zero,
                                                                              windows, win_ids, half_rows),
-                            nW, C, f, hw, dev, apg=apg)
+                            nW, C, f, hw, dev, apg=apg, reuse=reuse)
         self.last_schedule, self.last_guidance = guidance.schedule, guidance.report
         preds = torch.empty((nW, C, f, hw), device=dev, dtype=torch.float32)
         sampler = Sampler(self.scheduler, update, coefs, latents, begin_index, noise_seed)
@@ -589,7 +619,7 @@ class VExpressPipeline:
                  guidance_start: float = 0.0, guidance_end: float = 1.0, init_video=None, init_latents=None,
                  mask=None, composite=True, audio_guidance_scale: Optional[float] = None, overlap_blend="mean",
                  apg_eta: Optional[float] = None, apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0,
-                 **kwargs):
+                 guidance_refresh: int = 1, guidance_reuse: str = "hold", **kwargs):
         """Window stitch: `context_schedule` = "uniform" (the reference's; a clip length that is not f + k (f - o) ends in
         a reflected window with duplicate frames) or "uniform_fit" (the same number of windows spread evenly over any
         length); `overlap_blend` = "mean" (default, also None: the reference's 1 / count) or a weighted blend of the
@@ -605,6 +635,11 @@ class VExpressPipeline:
         `apg_norm_threshold` per frame (0: no cap) and averaged with `apg_momentum` (|.| < 1, usually negative) over the
         guided steps.  It acts on the model output per window and frame, with every row route and sampler; it cannot be
         combined with `guidance_rescale`, and without guidance it is ignored.
+        Guidance reuse (CFG-cache): `guidance_refresh` = k > 1 computes the guidance differences only on every k-th guided
+        step (and on the first and the last one); the guided steps between run the conditional row alone - the cost of an
+        unguided step - and add the stored differences, held (`guidance_reuse` = "hold", the default) or extrapolated
+        linearly from the last two refreshes ("linear").  It cannot be combined with `guidance_rescale` or `apg_eta`;
+        without guidance it is ignored; the effect on visual quality with real weights is not measured.
         Init-video sampling (diffusers' img2img / inpaint semantics for a 4-channel UNet): `init_video` fp32
         [1, 3, F, H, W] in [0, 1] (VAE-encoded here; needs v_express_amd.AutoencoderKL) or `init_latents`
         [1, 4, F, h, w] (clean, already scaled) makes the loop start from the clip noised to the level of `strength`
@@ -618,6 +653,7 @@ class VExpressPipeline:
         check_guidance(guidance_rescale, guidance_start, guidance_end, max(int(num_inference_steps), 1))
         audio_guidance_scale = check_audio_guidance(audio_guidance_scale)
         apg = check_apg((apg_eta, apg_norm_threshold, apg_momentum), guidance_rescale)
+        check_reuse(guidance_refresh, guidance_reuse, guidance_rescale, apg)
 
         def clip_windows():
             return list(get_context_scheduler(context_schedule)(
@@ -714,7 +750,8 @@ class VExpressPipeline:
         self.denoise(lat, kps_tokens, audio, timesteps, windows, guidance_scale, callback, callback_steps or 1,
                      begin_index=begin_index, eta=eta, noise_seed=noise_seed, guidance_rescale=guidance_rescale,
                      guidance_start=guidance_start, guidance_end=guidance_end, known=known,
-                     audio_guidance_scale=audio_guidance_scale, overlap_blend=overlap_blend, apg=apg)
+                     audio_guidance_scale=audio_guidance_scale, overlap_blend=overlap_blend, apg=apg,
+                     guidance_refresh=guidance_refresh, guidance_reuse=guidance_reuse)
         self.last_overlap["schedule"] = context_schedule
         if timed:
             ev[1].record()

@@ -9,6 +9,7 @@ buffers and host-side coefficients, so that a timestep reads straight down:
   Known     the known region of init-video sampling: the start latents and the blend after every step.
 A choice that does not depend on the timestep is made in a constructor (a method bound there), never in the loop.  Every
 kernel wrapper is looked up as `ops.<name>` when it is called: tests and tools replace them there."""
+import struct
 from typing import Any, List, NamedTuple
 
 import torch
@@ -19,6 +20,33 @@ from . import ops
 # row 1 real): "u" drops everything, "m" ("silent") keeps the reference bank and the keypoints and drops the audio, "c"
 # keeps everything.
 GUIDANCE_ROWS = {"u": (0, 0, 0), "m": (1, 1, 0), "c": (1, 1, 1)}
+
+
+REUSE_MODES = ("hold", "linear")
+
+
+def refresh_roles(guided, refresh):
+    """The role of every step under guidance reuse with the period `refresh`: None for an unguided step, "refresh" for a
+    guided step that runs all its rows - the first and the last guided step, and every guided step that `refresh` - 1
+    reuse steps precede since the last refresh - and "reuse" for the guided steps between, which run the conditional row
+    alone.  Unguided steps do not count towards the period."""
+    idx = [i for i, g in enumerate(guided) if g]
+    roles, since = [None] * len(guided), 0
+    for n, i in enumerate(idx):
+        if n == 0 or n == len(idx) - 1 or since == refresh - 1:
+            roles[i], since = "refresh", 0
+        else:
+            roles[i], since = "reuse", since + 1
+    return roles
+
+
+def reuse_coefficients(scales, w):
+    """(a_k, b_k) of a reuse step per guidance difference with the scale s_k: u + s (m - u) + s_a (c - m) rewritten around
+    c, c + sum (s_k - 1) d_k, with d_k extrapolated from the last two refreshes, d_k = (1 + w) L_k - w P_k: a_k =
+    (s_k - 1)(1 + w), b_k = -(s_k - 1) w.  Formed in double, each rounded to float32 once."""
+    def f32(v):
+        return struct.unpack("f", struct.pack("f", v))[0]
+    return [(f32((s - 1.0) * (1.0 + w)), f32(-(s - 1.0) * w) if w else 0.0) for s in scales]
 
 
 class UnitCall(NamedTuple):
@@ -84,11 +112,17 @@ class Guidance:
     window predictions: vx_combine_units, vx_combine_units3, vx_guidance_rescale, vx_guidance_rescale3 or - with
     `apg` = (eta, norm_threshold, momentum) - vx_guidance_apg, whose workspace and zero-initialised momentum buffers
     (`momentum`: one per guidance difference, advanced by the guided steps only) live here.
+    Guidance reuse, `reuse` = (refresh period k > 1, "hold" | "linear"): the guided steps take the roles of refresh_roles;
+    a refresh step runs the guided plan and vx_combine_units_keep, which also stores the differences of consecutive rows
+    in `slots` (float32 [1 or 2][rows - 1, nW, C, f, hw]; refresh number j writes slot j % 2 in the "linear" mode, the
+    one slot in the "hold" mode); a reuse step runs the conditional-only plan of an unguided step and vx_combine_reused
+    on the slots, with the coefficients of reuse_coefficients.  Unguided steps neither read nor advance the slots, which
+    are identical on every rank, like the momentum buffers.
     `unit_plan(half_rows)` builds a plan (VExpressPipeline._unit_plan, given the all-zero audio rows): collective, so both
     plans are built here, on every rank, before the loop.  `report` is last_guidance, `schedule` last_schedule."""
 
     def __init__(self, row_names, guidance_scale, audio_guidance_scale, rescale, guided, kps_tokens, audio, unit_plan,
-                 nW, C, f, hw, dev, apg=None):
+                 nW, C, f, hw, dev, apg=None, reuse=None):
         steps = len(guided)
         do_cfg = len(row_names) > 1                   # a guided step combines rows
         cond_rows = 2 if do_cfg else 1
@@ -105,7 +139,10 @@ class Guidance:
         # (the one-scale routes name their rows by index, as they always have; a silent row needs the triple)
         half_rows = [GUIDANCE_ROWS[r] for r in row_names] if "m" in row_names else list(range(cond_rows))
         self.plan_g = unit_plan(audio_is_zero, half_rows)
-        self.plan_c = None if all(guided) else unit_plan(audio_is_zero, [1])
+        # (a reuse step issues exactly an unguided step's UNet calls: the same plan object)
+        roles = refresh_roles(guided, reuse[0]) if reuse is not None and do_cfg else None
+        reusing = roles is not None and "reuse" in roles
+        self.plan_c = None if all(guided) and not reusing else unit_plan(audio_is_zero, [1])
         self.schedule = self.plan_g["schedule"]
         self.report = dict(guided_steps=sum(guided) if do_cfg else 0, steps=steps, rescale=rescale,
                            unguided_schedule=None if self.plan_c is None else self.plan_c["schedule"])
@@ -144,6 +181,42 @@ class Guidance:
             guided_op = combine2 if ws is None else rescale2
         self.plans = [self.plan_g if g else self.plan_c for g in guided]
         self.combines = [guided_op if g else conditional for g in guided]
+        self.slots = None
+        if reuse is not None:
+            self.report.update(refresh=reuse[0], reuse=reuse[1],
+                               refresh_steps=[i for i, r in enumerate(roles or []) if r == "refresh"])
+        if reusing:
+            scales = (s, s_a) if len(row_names) == 3 else (scale2,)
+            self._reuse(roles, reuse[1], scales, geo, (nW, C, f, hw), dev)
+
+    def _reuse(self, roles, mode, scales, geo, shape, dev):
+        """The plans and launches of the refresh and reuse steps (some step reuses): allocates the slots."""
+        nd = len(scales)
+        self.slots = torch.empty((2 if mode == "linear" else 1, nd) + shape, device=dev, dtype=torch.float32)
+        s, s_a = (scales + (0.0,))[:2]
+
+        def keep(slot):
+            def op(g, u, p): ops.combine_units_keep(g, u, *geo, s, s_a, slot, p)
+            return op
+
+        def reused(last, prev, coef):
+            (a1, b1), (a2, b2) = (coef + [(0.0, 0.0)])[:2]
+            prev = prev if b1 != 0.0 or b2 != 0.0 else None
+
+            def op(g, u, p): ops.combine_reused(g, u, *geo, last, prev, a1, b1, a2, b2, p)
+            return op
+        done = []                                     # the step indices of the refreshes so far
+        for i, role in enumerate(roles):
+            if role == "refresh":
+                self.combines[i] = keep(self.slots[len(done) % len(self.slots)])
+                done.append(i)
+            elif role == "reuse":
+                last = self.slots[(len(done) - 1) % len(self.slots)]
+                w = 0.0
+                if mode == "linear" and len(done) > 1:
+                    w = (i - done[-1]) / (done[-1] - done[-2])
+                self.plans[i] = self.plan_c
+                self.combines[i] = reused(last, self.slots[len(done) % len(self.slots)], reuse_coefficients(scales, w))
 
     def plan(self, i):
         return self.plans[i]
