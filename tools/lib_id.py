@@ -13,7 +13,8 @@ files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(C
                                                           os.path.join(ROOT, "include", "vexpress_hip_guidance.h"),
                                                           os.path.join(ROOT, "include", "vexpress_hip_samplers.h"),
                                                           os.path.join(ROOT, "include", "vexpress_hip_solvers.h"),
-                                                          os.path.join(ROOT, "include", "vexpress_hip_reuse.h")])
+                                                          os.path.join(ROOT, "include", "vexpress_hip_reuse.h"),
+                                                          os.path.join(ROOT, "include", "vexpress_hip_resize.h")])
 for path in files:
     h.update(os.path.basename(path).encode())
     with open(path, "rb") as f:

@@ -11,6 +11,8 @@ with a chosen sampler and step count (GPU box):
     python tools/sampler_bench.py --scheduler ddim --steps 25 --audio-guidance-scale 6 [--guidance-scale 1]
     python tools/sampler_bench.py --scheduler ddim --steps 25 --apg-eta 0 --apg-norm-threshold 20 --apg-momentum -0.5
     python tools/sampler_bench.py --scheduler ddim --steps 25 --guidance-refresh 2 [--guidance-reuse linear]
+    python tools/sampler_bench.py --scheduler ddim --steps 25 --size 768
+    python tools/sampler_bench.py --scheduler ddim --steps 25 --hires-size 768 [--hires-steps 15] [--hires-strength 0.5]
 Prints one JSON line: ms per clip (host clock around whole clips, ending in a device synchronise), the denoise and decode
 milliseconds of the same clips (HIP events), and the average microseconds of the per-step update launch (HIP events
 around each `ops.overlap_ddim_step` / `ops.overlap_multistep_step` / `ops.overlap_ancestral_step` /
@@ -39,7 +41,15 @@ step's, timed like the update launch, and `apg_combine_us` the plain combine of 
 --frames F --context-frames f --context-overlap o --context-schedule uniform|uniform_fit choose the clip length and its
 windows (defaults: 16 frames in one window of 16, overlap 4, `uniform`); --overlap-blend mean|linear|pyramid the stitch of
 overlapping windows - a weighted blend adds one `ops.overlap_blend` launch per step (`overlap_blend_us`, timed like the
-update launch, whose own time is then that of the trivial one-term plan)."""
+update launch, whose own time is then that of the trivial one-term plan).
+--size S samples an S x S clip instead of 512 x 512 (a multiple of 64).
+--hires-size S2 [--hires-steps N2] [--hires-strength T] [--hires-mode bilinear|bicubic] times two-pass (hi-res) clips: S x S
+with --steps, the latents resized to S2 x S2 and the last int(N2 * T) of N2 timesteps there, decoded at S2 x S2.  These
+clips run through `VExpressPipeline.__call__` on features (the public route of the feature), so a clip also holds what
+the other clips of this tool keep outside the timed region: the ReferenceNet run and the keypoint-token layout of each
+pass.  The line carries `pass1_ms`, `resize_us` (the one `vx_latent_resize` launch) and `pass2_ms` (HIP events of
+`pipe.hires_timings_ms()`: the two loops and the launch between them), `decode_ms`, and `other_ms`, the rest of the clip.
+The loop controls above are passed on; the per-launch columns are not collected in this mode."""
 import argparse
 import json
 import os
@@ -83,6 +93,12 @@ def main():
     ap.add_argument("--context-overlap", type=int, default=4)
     ap.add_argument("--context-schedule", choices=("uniform", "uniform_fit"), default="uniform")
     ap.add_argument("--overlap-blend", choices=("mean", "linear", "pyramid"), default="mean")
+    ap.add_argument("--size", type=int, default=512, help="pixel size of the (square) clip, a multiple of 64")
+    ap.add_argument("--hires-size", type=int, default=None,
+                    help="two-pass sampling: the pixel size of the second pass (through VExpressPipeline.__call__)")
+    ap.add_argument("--hires-steps", type=int, default=None, help="timesteps of the second pass's schedule (default: --steps)")
+    ap.add_argument("--hires-strength", type=float, default=0.5)
+    ap.add_argument("--hires-mode", choices=("bilinear", "bicubic"), default="bilinear")
     ap.add_argument("--clips", type=int, default=5, help="timed clips")
     ap.add_argument("--warmup", type=int, default=1)
     args = ap.parse_args()
@@ -92,6 +108,10 @@ def main():
         ap.error("--mask needs --init-video")
     if not 0.0 <= args.strength <= 1.0:
         ap.error("--strength must lie in [0, 1]")
+    if args.size < 64 or args.size % 64 or (args.hires_size is not None and (args.hires_size < 64 or args.hires_size % 64)):
+        ap.error("--size and --hires-size must be positive multiples of 64")
+    if args.hires_size is not None and (args.init_video or args.strength != 1.0):
+        ap.error("--hires-size starts its first pass from noise: no --init-video, no --strength")
     if not torch.cuda.is_available():
         raise SystemExit("sampler_bench.py measures on the GPU: no device visible")
     import v_express_amd as vx
@@ -101,7 +121,7 @@ def main():
     dev, elem = torch.device("cuda", 0), torch.bfloat16
     torch.cuda.set_device(dev)
     cfg, vcfg = synth.UNetConfig(), synth.VaeConfig()
-    F, h = args.frames, 64
+    F, h = args.frames, args.size // 8
     unet = vx.UNet3DConditionModel(cfg).to(dev).to(elem)
     refnet = vx.UNet2DConditionModel(cfg).to(dev).to(elem)
     vae = (vx.AutoencoderKL if args.init_video else vx.AutoencoderKLDecoder)(vcfg).to(dev).to(elem)
@@ -135,6 +155,8 @@ def main():
         sched, update = vx.DPMSolverMultistepScheduler(**kw, solver_order=args.order), "overlap_multistep_step"
     pipe = vx.VExpressPipeline(vae=vae, reference_net=refnet, denoising_unet=unet, scheduler=sched)
     inp = synth.synthetic_inputs(cfg, F, h, h, seed=42, device=dev)
+    if args.hires_size is not None:
+        return hires_bench(args, vx, pipe, cfg, inp, eta)
     writer = vx.ReferenceAttentionControl(refnet, do_classifier_free_guidance=True, mode="write", fusion_blocks="full")
     reader = vx.ReferenceAttentionControl(unet, do_classifier_free_guidance=True, mode="read", fusion_blocks="full",
                                           reference_attention_weight=0.95, audio_attention_weight=3.0)
@@ -207,7 +229,7 @@ def main():
     decode_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / args.clips
     per_clip = [e[0].elapsed_time(e[2]) for e in evs]
     encode_ms = round(sum(e[0].elapsed_time(e[3]) for e in evs) / args.clips, 2) if args.init_video else None
-    assert video.shape == (1, 3, F, 512, 512) and torch.isfinite(video).all()
+    assert video.shape == (1, 3, F, args.size, args.size) and torch.isfinite(video).all()
     # one more clip with events around every update launch (kept out of the timed clips above)
     def update_launch_us(name):
         orig, marks = getattr(ops, name), []
@@ -322,7 +344,7 @@ def main():
         scheduler=args.scheduler,
         order={"dpm": args.order, "lms": args.lms_order, "unipc": args.solver_order}.get(args.scheduler),
         eta=eta if args.scheduler == "ddim-eta" else None, steps=args.steps,
-        config=f"512x512, {F} frames ({'one window' if len(windows) == 1 else f'{len(windows)} windows'}), "
+        config=f"{args.size}x{args.size}, {F} frames ({'one window' if len(windows) == 1 else f'{len(windows)} windows'}), "
                f"CFG {args.guidance_scale:g}, synthetic weights, bf16",
         clips=args.clips,
         ms_per_clip=round(clip_ms, 2), denoise_ms=round(denoise_ms, 2), decode_ms=round(decode_ms, 2),
@@ -341,6 +363,60 @@ def main():
         context_overlap=args.context_overlap, context_schedule=args.context_schedule, windows=len(windows),
         overlap_blend=args.overlap_blend, overlap_blend_launches=wblend_launches,
         overlap_blend_us=None if wblend_us is None else round(wblend_us, 2), build=vx.lib.lib.vx_build_id().decode())))
+
+
+def hires_bench(args, vx, pipe, cfg, inp, eta):
+    """--hires-size: timed two-pass clips through VExpressPipeline.__call__ on features; prints the JSON line."""
+    from v_express_amd import synth
+    F, size2 = args.frames, args.hires_size
+    inp2 = synth.synthetic_inputs(cfg, F, size2 // 8, size2 // 8, seed=42, device=inp["latents"].device)
+    kw = dict(context_schedule=args.context_schedule, context_frames=args.context_frames,
+              context_overlap=args.context_overlap, reference_attention_weight=0.95, audio_attention_weight=3.0,
+              reference_latents=inp["ref_latents"], kps_features=inp["kps_features"],
+              audio_embeddings=inp["audio_embeddings"], latents=inp["latents"], eta=eta, noise_seed=12345,
+              guidance_rescale=args.guidance_rescale, guidance_start=args.guidance_start, guidance_end=args.guidance_end,
+              audio_guidance_scale=args.audio_guidance_scale, overlap_blend=args.overlap_blend,
+              guidance_refresh=args.guidance_refresh, guidance_reuse=args.guidance_reuse, output_device=None,
+              hires_size=(size2, size2), hires_steps=args.hires_steps, hires_strength=args.hires_strength,
+              hires_mode=args.hires_mode, hires_noise=inp2["latents"], hires_reference_latents=inp2["ref_latents"],
+              hires_kps_features=inp2["kps_features"])
+    if args.apg_eta is not None:
+        kw.update(apg_eta=args.apg_eta, apg_norm_threshold=args.apg_norm_threshold, apg_momentum=args.apg_momentum)
+
+    def one_clip():
+        return pipe(None, None, None, args.size, args.size, F, args.steps, args.guidance_scale, **kw)
+    for _ in range(args.warmup):
+        one_clip()
+    torch.cuda.synchronize()
+    parts, per_clip = [], []
+    t0 = time.perf_counter()
+    for _ in range(args.clips):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        video = one_clip()
+        e.record()
+        parts.append((pipe.last_hires["events"], pipe._events))
+        per_clip.append((s, e))
+    torch.cuda.synchronize()
+    clip_ms = 1e3 * (time.perf_counter() - t0) / args.clips
+    assert video.shape == (1, 3, F, size2, size2) and torch.isfinite(video).all()
+    per_clip = [s.elapsed_time(e) for s, e in per_clip]
+    pass1 = sum(h[0].elapsed_time(h[1]) for h, _ in parts) / args.clips
+    resize = sum(h[2].elapsed_time(h[3]) for h, _ in parts) / args.clips
+    pass2 = sum(h[4].elapsed_time(h[5]) for h, _ in parts) / args.clips
+    decode = sum(d[1].elapsed_time(d[2]) for _, d in parts) / args.clips
+    last = pipe.last_hires
+    print(json.dumps(dict(
+        scheduler=args.scheduler, steps=args.steps,
+        config=f"{args.size}x{args.size} -> {size2}x{size2}, {F} frames, CFG {args.guidance_scale:g}, synthetic weights, "
+               f"bf16, through __call__ on features",
+        clips=args.clips, ms_per_clip=round(clip_ms, 2), frames_per_s=round(F * 1e3 / clip_ms, 3),
+        clip_ms_min=round(min(per_clip), 2), clip_ms_max=round(max(per_clip), 2), pass1_ms=round(pass1, 2),
+        resize_us=round(1e3 * resize, 2), pass2_ms=round(pass2, 2), decode_ms=round(decode, 2),
+        other_ms=round(sum(per_clip) / args.clips - pass1 - resize - pass2 - decode, 2), hires_size=size2,
+        hires_steps=last["steps"], hires_strength=args.hires_strength, hires_mode=last["mode"],
+        hires_begin_index=last["begin_index"], hires_steps_run=last["steps"] - last["begin_index"], frames=F,
+        windows=pipe.last_overlap["windows"], build=vx.lib.lib.vx_build_id().decode())))
 
 
 if __name__ == "__main__":

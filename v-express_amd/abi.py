@@ -1,7 +1,7 @@
 """Reader of the C ABI header include/vexpress_hip.h: the ABI version, the enum constants, the parameter structs and the
 prototypes, as ctypes types.  lib.py binds both libraries from it, so the header is the only statement of the contract.
-include/vexpress_hip_guidance.h, include/vexpress_hip_samplers.h, include/vexpress_hip_solvers.h and
-include/vexpress_hip_reuse.h, the second to fifth header (entry points added without touching the earlier ones), are read
+include/vexpress_hip_guidance.h, include/vexpress_hip_samplers.h, include/vexpress_hip_solvers.h,
+include/vexpress_hip_reuse.h and include/vexpress_hip_resize.h, the second to sixth header (entry points added without touching the earlier ones), are read
 the same way.
 Pure Python: no torch, no shared library.  It fails closed: once comments, preprocessor lines, the extern "C" braces and
 every declaration it has understood are taken out, anything but whitespace left over is an ImportError naming it."""
@@ -16,6 +16,7 @@ GUIDANCE_HEADER = os.path.join(os.path.dirname(HEADER), "vexpress_hip_guidance.h
 SAMPLERS_HEADER = os.path.join(os.path.dirname(HEADER), "vexpress_hip_samplers.h")
 SOLVERS_HEADER = os.path.join(os.path.dirname(HEADER), "vexpress_hip_solvers.h")
 REUSE_HEADER = os.path.join(os.path.dirname(HEADER), "vexpress_hip_reuse.h")
+RESIZE_HEADER = os.path.join(os.path.dirname(HEADER), "vexpress_hip_resize.h")
 
 # version: int; enums: {name: value}; structs: {C name: [(field, ctypes type, array length or 0)]}; classes: {C name: the
 # ctypes.Structure built from those fields}; functions: {name: (restype, [(parameter, ctypes type)])}, all in header order
@@ -133,3 +134,10 @@ def reuse_header():
     """include/vexpress_hip_reuse.h, parsed once per process (version macro VX_REUSE_ABI_VERSION)."""
     with open(REUSE_HEADER) as f:
         return parse(f.read(), REUSE_HEADER, "VX_REUSE_ABI_VERSION")
+
+
+@functools.lru_cache(maxsize=None)
+def resize_header():
+    """include/vexpress_hip_resize.h, parsed once per process (version macro VX_RESIZE_ABI_VERSION)."""
+    with open(RESIZE_HEADER) as f:
+        return parse(f.read(), RESIZE_HEADER, "VX_RESIZE_ABI_VERSION")

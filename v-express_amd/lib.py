@@ -1,6 +1,6 @@
 """ctypes binding of libvexpress_hip.so (C ABI: include/vexpress_hip.h and, for the guidance and sampler entry points added
-after it, include/vexpress_hip_guidance.h, include/vexpress_hip_samplers.h, include/vexpress_hip_solvers.h and
-include/vexpress_hip_reuse.h).
+after it, include/vexpress_hip_guidance.h, include/vexpress_hip_samplers.h, include/vexpress_hip_solvers.h,
+include/vexpress_hip_reuse.h and include/vexpress_hip_resize.h).
 
 There is NO fallback: if the library is missing, unbuildable or lacks a symbol, importing this module
 raises.  The library is built in-tree (v-express_amd/libvexpress_hip.so) by `__graft_entry__.build()` /
@@ -21,6 +21,7 @@ GUIDANCE_HEADER = abi.GUIDANCE_HEADER
 SAMPLERS_HEADER = abi.SAMPLERS_HEADER
 SOLVERS_HEADER = abi.SOLVERS_HEADER
 REUSE_HEADER = abi.REUSE_HEADER
+RESIZE_HEADER = abi.RESIZE_HEADER
 
 # the binding is DERIVED from the header (abi.py reads it once per process): the enum constants, the ctypes mirrors of the
 # four parameter structs and, in _load, argtypes / restype of every function - there is no second copy to keep in step
@@ -50,12 +51,13 @@ def _load(path=None, element="bf16"):
         raise ImportError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(or `make -C v-express_amd/csrc`).  There is no CPU fallback.")
     lib = C.CDLL(path)
-    # the five headers, each with its own version: the first one's, then the guidance, sampler, solver and guidance-reuse
-    # entry points
+    # the six headers, each with its own version: the first one's, then the guidance, sampler, solver, guidance-reuse
+    # and latent-resize entry points
     for hdr, version in ((abi.header(), "vx_abi_version"), (abi.guidance_header(), "vx_guidance_abi_version"),
                          (abi.samplers_header(), "vx_samplers_abi_version"),
                          (abi.solvers_header(), "vx_solvers_abi_version"),
-                         (abi.reuse_header(), "vx_reuse_abi_version")):
+                         (abi.reuse_header(), "vx_reuse_abi_version"),
+                         (abi.resize_header(), "vx_resize_abi_version")):
         missing = [s for s in sorted(hdr.functions) if not hasattr(lib, s)]
         if missing:
             raise ImportError(f"{path} does not export {missing}; rebuild it")
@@ -120,14 +122,15 @@ class element_type:
 
 def source_id():
     """sha256 (first 16 hex digits) over the kernel sources the library is built from - csrc/*.hip / *.h / *.cpp and the
-    five C ABI headers, in name order.  (Of the sources, not of the .so: a rebuild on another machine need not be
+    six C ABI headers, in name order.  (Of the sources, not of the .so: a rebuild on another machine need not be
     byte-identical, the sources it was built from are.  tools/lib_id.py prints the same value without importing torch.)"""
     import glob
     import hashlib
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")) +
                    glob.glob(os.path.join(CSRC, "*.cpp")) + [os.path.join(CSRC, "Makefile"), HEADER, GUIDANCE_HEADER,
-                                                              SAMPLERS_HEADER, SOLVERS_HEADER, REUSE_HEADER])
+                                                              SAMPLERS_HEADER, SOLVERS_HEADER, REUSE_HEADER,
+                                                              RESIZE_HEADER])
     try:
         for path in files:
             h.update(os.path.basename(path).encode())

@@ -1,11 +1,13 @@
 """Tensor-level wrappers around the C ABI (include/vexpress_hip.h, include/vexpress_hip_guidance.h,
-include/vexpress_hip_samplers.h, include/vexpress_hip_solvers.h, include/vexpress_hip_reuse.h).
+include/vexpress_hip_samplers.h, include/vexpress_hip_solvers.h, include/vexpress_hip_reuse.h,
+include/vexpress_hip_resize.h).
 
 PyTorch is used for device memory and streams only: every wrapper passes raw device pointers, explicit
 shapes/strides and `torch.cuda.current_stream()` to libvexpress_hip.so.  Activations are bf16
 channels-last tokens `[frames, H*W, C]`; weights are pre-laid-out by `weights.py`.
 """
 import ctypes as C
+import functools
 import logging
 import math
 import os
@@ -1681,6 +1683,72 @@ def known_blend(latents, init, noise, mask, a, s):
         raise ValueError(f"known_blend: the signal / noise pair must not be negative, got ({a}, {s})")
     L.check(_lib.vx_known_blend(_ptr(latents), _ptr(init), _ptr(noise), _ptr(mask), c, F, h * w, a, s, _stream()),
             "vx_known_blend")
+
+
+RESIZE_MODES = ("bilinear", "bicubic")
+_RESIZE_TABLES = {}
+
+
+@functools.lru_cache(maxsize=None)
+def resize_taps(n_in, n_out, mode):
+    """The taps of one axis of `latent_resize`, resolved in float64 on the host: (indices int64 [n_out, taps], weights
+    float64 [n_out, taps]) with torch.nn.functional.interpolate's align_corners=False, antialias=False coordinates,
+    s = (n_in / n_out) (d + 0.5) - 0.5.  "bilinear" (2 taps): s clamped at 0, i0 = min(floor(s), n_in - 1), i1 = min(i0 + 1,
+    n_in - 1), weights (1 - t, t), t = s - i0.  "bicubic" (4 taps): s as it is, i = floor(s), the taps i - 1 .. i + 2
+    clamped into [0, n_in - 1], weights the cubic convolution (A = -0.75) of t = s - i."""
+    if mode not in RESIZE_MODES:
+        raise ValueError(f"latent_resize: mode must be one of {RESIZE_MODES}, got {mode!r}")
+    d = torch.arange(n_out, dtype=torch.float64)
+    s = (n_in / n_out) * (d + 0.5) - 0.5
+    if mode == "bilinear":
+        s = s.clamp_min(0.0)
+        i0 = s.floor().clamp_max(n_in - 1)
+        t = s - i0
+        idx = torch.stack([i0, (i0 + 1).clamp_max(n_in - 1)], dim=1)
+        return idx.long(), torch.stack([1.0 - t, t], dim=1)
+    i = s.floor()
+    t = s - i
+    A = -0.75
+
+    def near(x):                                  # |x| <= 1
+        return ((A + 2.0) * x - (A + 3.0)) * x * x + 1.0
+    # the outer taps, A (|x| - 1) (|x| - 2)^2 at |x| = 1 + t and 2 - t, in the factored form: expanded in |x| the terms
+    # cancel from 6 down to 0.1 and the four weights miss the sum 1 by up to 1e-15
+    wts = torch.stack([A * t * (1.0 - t) * (1.0 - t), near(t), near(1.0 - t), A * (1.0 - t) * t * t], dim=1)
+    idx = torch.stack([i - 1, i, i + 1, i + 2], dim=1).clamp(0, n_in - 1)
+    return idx.long(), wts
+
+
+def latent_resize(latents, size, mode="bilinear"):
+    """Latent resize (vx_latent_resize, include/vexpress_hip_resize.h): latents fp32 [1, C, F, h, w] -> a new fp32
+    [1, C, F, h2, w2], size = (h2, w2), every (channel, frame) plane on its own, with the semantics of
+    torch.nn.functional.interpolate(mode=mode, align_corners=False, antialias=False); mode "bilinear" or "bicubic"
+    (A = -0.75); any ratio, up or down.  The tap tables are `resize_taps`' float64 values rounded once to float32, kept
+    on the device per (h, w, h2, w2, mode)."""
+    if not isinstance(latents, torch.Tensor) or latents.dtype != torch.float32 or not latents.is_contiguous():
+        raise TypeError("latent_resize: contiguous float32 latents expected")
+    if latents.dim() != 5 or latents.shape[0] != 1:
+        raise ValueError(f"latent_resize: latents must be [1, C, F, h, w], got {tuple(latents.shape)}")
+    if mode not in RESIZE_MODES:
+        raise ValueError(f"latent_resize: mode must be one of {RESIZE_MODES}, got {mode!r}")
+    try:
+        h2, w2 = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"latent_resize: size must be (h2, w2), got {size!r}") from None
+    _, c, F, h, w = latents.shape
+    if min(c, F, h, w) < 1 or h2 < 1 or w2 < 1:
+        raise ValueError(f"latent_resize: sizes must be positive, got {tuple(latents.shape)} -> ({h2}, {w2})")
+    key = (h, w, h2, w2, mode, latents.device)
+    if key not in _RESIZE_TABLES:
+        (iy, wy), (ix, wx) = resize_taps(h, h2, mode), resize_taps(w, w2, mode)
+        _RESIZE_TABLES[key] = tuple(t.to(device=latents.device, dtype=dt).contiguous()
+                                    for t, dt in ((iy, torch.int32), (wy, torch.float32), (ix, torch.int32),
+                                                  (wx, torch.float32)))
+    iy, wy, ix, wx = _RESIZE_TABLES[key]
+    out = torch.empty((1, c, F, h2, w2), device=latents.device, dtype=torch.float32)
+    L.check(_lib.vx_latent_resize(_ptr(latents), c * F, h, w, _ptr(out), h2, w2, _ptr(iy), _ptr(wy), _ptr(ix), _ptr(wx),
+                                  wy.shape[1], _stream()), "vx_latent_resize")
+    return out
 
 
 def ncfhw_to_nhwc(x, c_pad=None):

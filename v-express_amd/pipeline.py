@@ -17,6 +17,7 @@ kernels when the v_express_amd classes are passed (prologue.py, vae.AutoencoderK
 transformers module.  The benchmark and the loop parity tests pass the prologue outputs in directly
 (`reference_latents=`, `kps_features=`, `audio_embeddings=`, `latents=` keyword arguments).
 """
+from types import SimpleNamespace
 from typing import Callable, List, Optional, Union
 
 import math
@@ -174,6 +175,51 @@ def check_init(init_video, init_latents, mask, video_length, height, width, scal
     return m
 
 
+def check_hires(hires_size, hires_steps, hires_strength, hires_mode, num_inference_steps, scale, init_given=False,
+                features=(None, None), hires_features=(None, None), hires_noise=None, video_length=None, channels=4):
+    """Validates the two-pass (hi-res) arguments of __call__ (ValueError); returns None without `hires_size`, else
+    dict(size=(width2, height2), steps, begin_index, mode).  `scale`: the VAE's; `features` / `hires_features`: the
+    caller's (reference_latents, kps_features) of the two sizes."""
+    names = ("hires_reference_latents", "hires_kps_features")
+    if hires_size is None:
+        for name, v in zip(names + ("hires_noise",), tuple(hires_features) + (hires_noise,)):
+            if v is not None:
+                raise ValueError(f"{name} belongs to the second pass of hi-res sampling: pass hires_size with it")
+        return None
+    try:
+        width2, height2 = hires_size
+        ok = all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in (width2, height2))
+    except (TypeError, ValueError):
+        ok = False
+    # the UNet's own rule for width / height: three 2x resampling stages under the VAE's factor
+    if not ok or min(width2, height2) < 1 or width2 % (8 * scale) or height2 % (8 * scale):
+        raise ValueError(f"hires_size must be (width2, height2), positive multiples of {8 * scale} as width and height "
+                         f"are, got {hires_size!r}")
+    if init_given:
+        raise ValueError("hires_size together with init_video / init_latents / mask: the second pass starts from the "
+                         "first one's clip, the first from noise; pass one of them")
+    if hires_mode not in ops.RESIZE_MODES:
+        raise ValueError(f"hires_mode must be one of {ops.RESIZE_MODES}, got {hires_mode!r}")
+    steps = num_inference_steps if hires_steps is None else hires_steps
+    if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or steps < 1:
+        raise ValueError(f"hires_steps must be a positive integer, got {hires_steps!r}")
+    if not isinstance(hires_strength, numbers.Real) or not 0.0 < float(hires_strength) <= 1.0:
+        raise ValueError(f"hires_strength must lie in (0, 1], got {hires_strength!r}")
+    run = int(steps * hires_strength)
+    if run == 0:
+        raise ValueError(f"hires_steps = {steps} at hires_strength = {hires_strength} leaves the second pass no step to "
+                         f"run (int(hires_steps * hires_strength) == 0)")
+    for name, first, second in zip(names, features, hires_features):
+        if first is not None and second is None:
+            raise ValueError(f"{name[6:]} was given for the first size: the second pass needs {name} at "
+                             f"{width2} x {height2} (or pass images for both)")
+    if hires_noise is not None:
+        want = (1, channels, int(video_length), height2 // scale, width2 // scale)
+        if not isinstance(hires_noise, torch.Tensor) or tuple(hires_noise.shape) != want:
+            raise ValueError(f"hires_noise must be a {list(want)} tensor, got {tuple(getattr(hires_noise, 'shape', ()))}")
+    return dict(size=(int(width2), int(height2)), steps=int(steps), begin_index=int(steps) - run, mode=hires_mode)
+
+
 def latent_mask(pixel_mask, video_length, scale):
     """The latent mask of a pixel mask (float32 [F or 1, H, W]): the scale x scale box mean, one row per frame,
     float32 [F, (H / scale) * (W / scale)].  A hard pixel edge inside a latent cell becomes a soft latent edge."""
@@ -221,6 +267,10 @@ class VExpressPipeline:
         # ("mean", "linear", "pyramid" or "profile"), the number of windows, the most predictions summed into one frame
         # and the vx_overlap_blend launches of the call (one per timestep of a weighted blend; 0 on the mean route)
         self.last_overlap = {}
+        # two-pass (hi-res) sampling of the last __call__: None without hires_size, else dict(base = (width, height),
+        # size = (width2, height2), mode, steps, begin_index (of the second pass), base_latents (the first pass's result,
+        # on the device), events (six HIP events, None off the GPU: hires_timings_ms reads them))
+        self.last_hires = None
         # batch rows per UNet call: 2 = the two CFG halves of one window; 4 (default), 6, ... also merge consecutive
         # windows of this rank into one call.  Every kernel is batch-invariant, so the rows come out bit-identical;
         # merged calls measure 4-5 % faster (profiles/r02e_host_overhead.json: b = 3 74.0 ms vs 49.2 + 28.2 ms,
@@ -619,7 +669,9 @@ class VExpressPipeline:
                  guidance_start: float = 0.0, guidance_end: float = 1.0, init_video=None, init_latents=None,
                  mask=None, composite=True, audio_guidance_scale: Optional[float] = None, overlap_blend="mean",
                  apg_eta: Optional[float] = None, apg_norm_threshold: float = 0.0, apg_momentum: float = 0.0,
-                 guidance_refresh: int = 1, guidance_reuse: str = "hold", **kwargs):
+                 guidance_refresh: int = 1, guidance_reuse: str = "hold", hires_size=None,
+                 hires_steps: Optional[int] = None, hires_strength: float = 0.5, hires_mode: str = "bilinear",
+                 hires_noise=None, hires_reference_latents=None, hires_kps_features=None, **kwargs):
         """Window stitch: `context_schedule` = "uniform" (the reference's; a clip length that is not f + k (f - o) ends in
         a reflected window with duplicate frames) or "uniform_fit" (the same number of windows spread evenly over any
         length); `overlap_blend` = "mean" (default, also None: the reference's 1 / count) or a weighted blend of the
@@ -646,7 +698,19 @@ class VExpressPipeline:
         instead of from pure noise; `mask` ([F or 1, 1, H, W] or [F or 1, H, W], float or bool in [0, 1]; 1 =
         regenerate, 0 = keep) restricts the change to a region (its 8 x 8 box mean is the latent mask), and with
         `init_video` and `composite` the kept pixels of the output are the caller's own, not their VAE round trip.
-        `latents` / `generator` give the N(0,1) noise, as without an init clip."""
+        `latents` / `generator` give the N(0,1) noise, as without an init clip.
+        Two-pass (hi-res) sampling: `hires_size` = (width2, height2) (default None: off) samples the clip at
+        (width, height) as without it, resizes the latents on the device (`ops.latent_resize`, `hires_mode` "bilinear" or
+        "bicubic"), noises them to the level of `hires_strength` and runs the last int(hires_steps * hires_strength) of
+        `hires_steps` timesteps (default: num_inference_steps) at the new size - the init-latents route above, with
+        ReferenceNet banks and keypoint tokens built at the new size from the images (or from
+        `hires_reference_latents` / `hires_kps_features` when the first pass was given features) and the audio embeddings
+        of the first pass.  `hires_noise` is the N(0,1) tensor of the second pass, as `latents` is of the first;
+        `generator` is drawn from in the order pass-1 latents, pass-1 ancestral seed, pass-2 noise, pass-2 ancestral
+        seed, and an explicit `noise_seed` gives the second pass noise_seed + 1.  The callback's step index runs on
+        through both passes.  decode=False returns the second pass's latents; `last_hires` reports the run.  Not
+        together with init_video / init_latents / mask; PNDM cannot start inside its schedule (NotImplementedError).
+        The effect on visual quality with real weights is not measured."""
         # an unsupported scheduler, eta with one other than DDIM, guidance controls out of range or init-video arguments
         # that do not fit the clip fail here, before the prologue
         ancestral = self._sampler(eta) == "ancestral"
@@ -654,6 +718,10 @@ class VExpressPipeline:
         audio_guidance_scale = check_audio_guidance(audio_guidance_scale)
         apg = check_apg((apg_eta, apg_norm_threshold, apg_momentum), guidance_rescale)
         check_reuse(guidance_refresh, guidance_reuse, guidance_rescale, apg)
+        hires = check_hires(hires_size, hires_steps, hires_strength, hires_mode, num_inference_steps,
+                            self.vae_scale_factor, not (init_video is None and init_latents is None and mask is None),
+                            (reference_latents, kps_features), (hires_reference_latents, hires_kps_features),
+                            hires_noise, video_length, self.denoising_unet.in_channels)
 
         def clip_windows():
             return list(get_context_scheduler(context_schedule)(
@@ -673,9 +741,74 @@ class VExpressPipeline:
             raise NotImplementedError("this VAE has no encoder half (AutoencoderKLDecoder): construct "
                                       "v_express_amd.AutoencoderKL and load encoder.* / quant_conv.*, or pass "
                                       "init_latents=[1,4,F,h/8,w/8] (already scaled by 0.18215)")
+        # the arguments both passes of a hi-res call share; `audio_embeddings` and `windows` are filled in by the first
+        # pass, where they have always been computed, and found there by the second
+        c = SimpleNamespace(
+            reference_image=reference_image, kps_images=kps_images, audio_waveform=audio_waveform,
+            video_length=video_length, guidance_scale=guidance_scale, eta=eta, generator=generator,
+            num_images_per_prompt=num_images_per_prompt, context_schedule=context_schedule, clip_windows=clip_windows,
+            windows=windows, reference_attention_weight=reference_attention_weight,
+            audio_attention_weight=audio_attention_weight, num_pad_audio_frames=num_pad_audio_frames,
+            audio_embeddings=audio_embeddings, ancestral=ancestral, guidance_rescale=guidance_rescale,
+            guidance_start=guidance_start, guidance_end=guidance_end, audio_guidance_scale=audio_guidance_scale,
+            overlap_blend=overlap_blend, apg=apg, guidance_refresh=guidance_refresh, guidance_reuse=guidance_reuse,
+            # the CFG layout of banks and conditioning (row 0 zeros, row 1 real): whenever a guided step combines rows
+            do_cfg=len(guidance_rows(guidance_scale, audio_guidance_scale)) > 1)
         dev = self.device
-        # the CFG layout of banks and conditioning (row 0 zeros, row 1 real): whenever a guided step combines rows
-        do_cfg = len(guidance_rows(guidance_scale, audio_guidance_scale)) > 1
+        self.last_hires = None
+        if hires is None:
+            lat, video_dev, ev, _ = self._sample_pass(c, width, height, num_inference_steps, strength, reference_latents,
+                                                      kps_features, latents, init_video, init_latents, pixel_mask,
+                                                      noise_seed, callback, callback_steps or 1)
+        else:
+            # the second pass's start is checked before the first one's prologue (PNDM: NotImplementedError)
+            self.scheduler.set_timesteps(hires["steps"])
+            self.scheduler.loop_steps(self.scheduler.timesteps[hires["begin_index"]:].tolist(), hires["begin_index"], eta,
+                                      init=True)
+            width2, height2 = hires["size"]
+            base, _, ev1, n1 = self._sample_pass(c, width, height, num_inference_steps, strength, reference_latents,
+                                                 kps_features, latents, None, None, None, noise_seed, callback,
+                                                 callback_steps or 1)
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if ev1 else None
+            if marks:
+                marks[0].record()
+            resized = ops.latent_resize(base, (height2 // self.vae_scale_factor, width2 // self.vae_scale_factor),
+                                        hires["mode"])
+            if marks:
+                marks[1].record()
+            every, cb2 = callback_steps or 1, None
+            if callback is not None:
+                def cb2(i, t, x):                        # the step index runs on through both passes
+                    if (n1 + i) % every == 0:
+                        callback(n1 + i, t, x)
+            lat, video_dev, ev, _ = self._sample_pass(c, width2, height2, hires["steps"], hires_strength,
+                                                      hires_reference_latents, hires_kps_features, hires_noise, None,
+                                                      resized, None, None if noise_seed is None else noise_seed + 1,
+                                                      cb2, 1)
+            self.last_hires = dict(hires, base=(int(width), int(height)), base_latents=base,
+                                   events=None if marks is None else (ev1[0], ev1[1], marks[0], marks[1], ev[0], ev[1]))
+        if not decode:
+            return lat
+        comp = None
+        if composite and video_dev is not None and pixel_mask is not None:
+            # the kept pixels are the caller's own: a VAE round trip must not degrade them
+            comp = (video_dev, pixel_mask.reshape(pixel_mask.shape[0], -1).to(dev).contiguous())
+        video = self.decode_latents(lat, composite=comp)
+        if ev:
+            ev[2].record()
+        self._events = ev
+        if output_device is not None:
+            video = video.to(output_device)
+        return video
+
+    def _sample_pass(self, c, width, height, num_inference_steps, strength, reference_latents, kps_features, latents,
+                     init_video, init_latents, pixel_mask, noise_seed, callback, callback_steps):
+        """One sampling pass of __call__ at (width, height): timesteps, ReferenceNet banks, keypoint tokens, the start
+        latents and the loop.  `c`: the arguments of the call that do not depend on the size (a namespace; this pass
+        fills in `audio_embeddings` and `windows` if they are still missing).  Returns (latents, the init video on the
+        device or None, the three timing events or None, the number of timesteps run)."""
+        dev = self.device
+        do_cfg, video_length, generator, eta = c.do_cfg, c.video_length, c.generator, c.eta
         # timesteps (retrieve_timesteps + get_timesteps, :448-449)
         self.scheduler.set_timesteps(num_inference_steps)
         init_t = min(int(num_inference_steps * strength), num_inference_steps)
@@ -687,28 +820,28 @@ class VExpressPipeline:
                                            batch_size=1, fusion_blocks="full")
         reader = ReferenceAttentionControl(self.denoising_unet, do_classifier_free_guidance=do_cfg, mode="read",
                                            batch_size=1, fusion_blocks="full",
-                                           reference_attention_weight=reference_attention_weight,
-                                           audio_attention_weight=audio_attention_weight)
+                                           reference_attention_weight=c.reference_attention_weight,
+                                           audio_attention_weight=c.audio_attention_weight)
         if reference_latents is None:
-            reference_latents = self.prepare_reference_latent(reference_image, height, width)
+            reference_latents = self.prepare_reference_latent(c.reference_image, height, width)
         kps_tokens = None
         if kps_features is None:
             if hasattr(self.v_kps_guider, "forward_tokens"):
-                kps_tokens = self.prepare_kps_tokens(kps_images, height, width, do_cfg)   # stays in the token layout
+                kps_tokens = self.prepare_kps_tokens(c.kps_images, height, width, do_cfg)   # stays in the token layout
             else:
-                kps_features = self.prepare_kps_feature(kps_images, height, width, do_cfg)
-        if audio_embeddings is None:
-            audio_embeddings = self.prepare_audio_embeddings(audio_waveform, video_length, num_pad_audio_frames,
-                                                             do_cfg)
-        if windows is None:
-            windows = clip_windows()
+                kps_features = self.prepare_kps_feature(c.kps_images, height, width, do_cfg)
+        if c.audio_embeddings is None:
+            c.audio_embeddings = self.prepare_audio_embeddings(c.audio_waveform, video_length, c.num_pad_audio_frames,
+                                                               do_cfg)
+        if c.windows is None:
+            c.windows = c.clip_windows()
         # ReferenceNet once per clip (:502-509)
         ehs0 = torch.zeros((1, 1, self.denoising_unet.cfg.cross_attention_dim), dtype=torch.float32, device=dev)
         self.reference_net(reference_latents.to(dev), timestep=0, encoder_hidden_states=ehs0, return_dict=False)
         reader.update(writer, do_cfg, dtype=self.dtype)
         known = video_dev = None
         if init_video is None and init_latents is None:
-            lat = self.prepare_latents(num_images_per_prompt, self.denoising_unet.in_channels, width, height,
+            lat = self.prepare_latents(c.num_images_per_prompt, self.denoising_unet.in_channels, width, height,
                                        video_length, self.dtype, dev, generator, latents)
             if self.dist.enabled and latents is None:
                 # every rank drew from its own CPU generator; the loop needs identical step-start latents on all ranks
@@ -731,7 +864,7 @@ class VExpressPipeline:
             m = None if pixel_mask is None else latent_mask(pixel_mask, video_length, self.vae_scale_factor).to(dev)
             known = (init, noise, m)
             lat = torch.empty_like(noise)
-        if ancestral and noise_seed is None:
+        if c.ancestral and noise_seed is None:
             # the ancestral noise is drawn on the device from one 64-bit seed, taken from the generator AFTER the
             # initial latents (which so stay what they are for a given generator); rank 0's seed wins, like its latents
             g = generator[0] if isinstance(generator, list) else generator
@@ -742,37 +875,31 @@ class VExpressPipeline:
         if kps_tokens is None:
             b2, c0, F, h, w = kps_features.shape
             kps_tokens = ops.ncfhw_to_nhwc(kps_features.to(dev), c0).view(b2, F, h * w, c0)
-        audio = audio_embeddings.to(device=dev, dtype=ops.BF16).contiguous()
+        audio = c.audio_embeddings.to(device=dev, dtype=ops.BF16).contiguous()
         timed = lat.is_cuda          # (host-logic tests run this method on CPU tensors over emulated kernels)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timed else None
         if timed:
             ev[0].record()
-        self.denoise(lat, kps_tokens, audio, timesteps, windows, guidance_scale, callback, callback_steps or 1,
-                     begin_index=begin_index, eta=eta, noise_seed=noise_seed, guidance_rescale=guidance_rescale,
-                     guidance_start=guidance_start, guidance_end=guidance_end, known=known,
-                     audio_guidance_scale=audio_guidance_scale, overlap_blend=overlap_blend, apg=apg,
-                     guidance_refresh=guidance_refresh, guidance_reuse=guidance_reuse)
-        self.last_overlap["schedule"] = context_schedule
+        self.denoise(lat, kps_tokens, audio, timesteps, c.windows, c.guidance_scale, callback, callback_steps,
+                     begin_index=begin_index, eta=eta, noise_seed=noise_seed, guidance_rescale=c.guidance_rescale,
+                     guidance_start=c.guidance_start, guidance_end=c.guidance_end, known=known,
+                     audio_guidance_scale=c.audio_guidance_scale, overlap_blend=c.overlap_blend, apg=c.apg,
+                     guidance_refresh=c.guidance_refresh, guidance_reuse=c.guidance_reuse)
+        self.last_overlap["schedule"] = c.context_schedule
         if timed:
             ev[1].record()
         reader.clear()
         writer.clear()
-        if not decode:
-            return lat
-        comp = None
-        if composite and video_dev is not None and pixel_mask is not None:
-            # the kept pixels are the caller's own: a VAE round trip must not degrade them
-            comp = (video_dev, pixel_mask.reshape(pixel_mask.shape[0], -1).to(dev).contiguous())
-        video = self.decode_latents(lat, composite=comp)
-        if timed:
-            ev[2].record()
-        self._events = ev
-        if output_device is not None:
-            video = video.to(output_device)
-        return video
+        return lat, video_dev, ev, len(timesteps)
 
     def timings_ms(self):
-        """(denoise loop, decode) GPU milliseconds of the last call."""
+        """(denoise loop, decode) GPU milliseconds of the last call (a hi-res call: the loop of its second pass)."""
         e = self._events
         e[2].synchronize()
         return e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2])
+
+    def hires_timings_ms(self):
+        """(first pass's loop, latent resize, second pass's loop) GPU milliseconds of the last hi-res call."""
+        e = self.last_hires["events"]
+        e[5].synchronize()
+        return e[0].elapsed_time(e[1]), e[2].elapsed_time(e[3]), e[4].elapsed_time(e[5])
